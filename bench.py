@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mix-StAGE train-step clips/sec (B=32 per GPU, T=64, 128-mel, 104-dim pose, M=S=8).
 
-    python bench.py --gpus N --steps K --warmup W [--precision fp32|bf16x6|bf16]
+    python bench.py --gpus N --steps K --warmup W [--precision fp32|bf16x6|bf16] [--dump-outputs DIR] [--full]
 
 With N > 1 and no launcher in the environment the script starts the N ranks itself (fresh child processes of
 `python -m torch.distributed.run`, started BEFORE this process touches the GPU); under a launcher (RANK / WORLD_SIZE set) it
@@ -11,8 +11,12 @@ One "step" = one reference train step (trainer.py:604-674 contract, see mix_stag
 GAN.forward (D-step or G-step by the reference's seeded host coin flip, gan.py:105) -> backward -> gradient all-reduce
 (N>1) -> clip_grad_norm_(.,1) -> Adam(1e-4).  Inputs are synthetic, resident in HBM before the timed region; weights are
 the name-keyed deterministic fill.  The curriculum is pinned to the audio branch (thresh = 1), as stated in
-BASELINE.md.  Prints ONE JSON line on rank 0: `value` over exactly K timed steps of the coin-flip sequence, plus (outside
-the timed region) G-step and D-step times measured separately and their 50/50 blend.
+BASELINE.md.  Prints ONE JSON line on rank 0: `value` and `ms_per_step` over exactly K timed steps of the coin-flip sequence.
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs DIR: the losses, the generated
+poses, a fixed sample of the updated weights and the BatchNorm buffers, as .npy) and prints the line.  --full adds, outside the
+timed region: G-step and D-step times measured separately and their 50/50 blend, the per-kernel table and roofline entries,
+the measured peaks, the bf16 mode beside an fp32 run, and the CPU oracle baseline.
 """
 import argparse
 import hashlib
@@ -54,10 +58,15 @@ def parse():
   ap.add_argument('--steps', type=int, default=60)
   ap.add_argument('--warmup', type=int, default=10)
   ap.add_argument('--no-graphs', action='store_true', help='eager launches instead of HIP-graph replay')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
-  ap.add_argument('--no-kernel-timing', action='store_true')
-  ap.add_argument('--no-per-kind', action='store_true', help='skip the separate G-step / D-step timing')
-  ap.add_argument('--no-bf16-extra', action='store_true', help='skip the extra bf16-mode measurement attached to the fp32 line')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure, after the timed steps: per-kind step times, per-kernel table and roofline, measured peaks, '
+                       'the bf16 mode beside fp32, the CPU oracle baseline (off: the headline figure only)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write what the last timed step computed to DIR/<name>.npy (float32 / float64, < 64 MB)')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU oracle baseline')
+  ap.add_argument('--no-kernel-timing', action='store_true', help='(--full) skip the per-kernel table and roofline')
+  ap.add_argument('--no-per-kind', action='store_true', help='(--full) skip the separate G-step / D-step timing')
+  ap.add_argument('--no-bf16-extra', action='store_true', help='(--full) skip the extra bf16-mode measurement attached to the fp32 line')
   ap.add_argument('--seed', type=int, default=4321)
   ap.add_argument('--config', default='headline', choices=sorted(CONFIGS), help='headline (default, the metric) | c2 | c4 | c5: BASELINE configs[1], [3], [4]')
   ap.add_argument('--precision', default=None, choices=['fp32', 'bf16x6', 'bf16'],
@@ -516,6 +525,53 @@ def time_steps(ts, batch, n, kind, world, dist, dev):
   return elapsed, kinds
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20       # elements kept of a larger array: a fixed seeded sample, the same positions in every run
+
+
+def _fixed_sample(n, seed=0):
+  import numpy as np
+  if n <= DUMP_SAMPLE:
+    return None
+  return np.sort(np.random.default_rng(seed).choice(n, size=DUMP_SAMPLE, replace=False))
+
+
+def save_outputs(dirpath, arrays):
+  """arrays: (name, tensor / ndarray) -> dirpath/<name>.npy in float32 (float64 stays float64)."""
+  import numpy as np
+  import torch
+  os.makedirs(dirpath, exist_ok=True)
+  out = []
+  for name, a in arrays:
+    if isinstance(a, torch.Tensor):
+      a = a.detach()
+      a = (a.double() if a.dtype == torch.float64 else a.float()).cpu().numpy()
+    a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    out.append((name, a))
+  total = sum(a.nbytes for _, a in out)
+  if total > DUMP_LIMIT_BYTES:
+    raise SystemExit('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_LIMIT_BYTES))
+  for name, a in out:
+    np.save(os.path.join(dirpath, name + '.npy'), a)
+
+
+def dump_train_outputs(dirpath, ts, model):
+  """What a caller of the timed train step holds after its last step: the losses (reference order), the generated poses, and
+  the model it updated -- the generator's parameters as a fixed sample of 2^20 positions of their concatenation in module order
+  (80.6 MB in full), the discriminator's parameters and every floating-point buffer (BatchNorm running statistics) whole."""
+  import torch
+  with torch.no_grad():
+    losses = torch.stack([l.detach().double().reshape(()).cpu() for l in ts.losses])
+    g = torch.cat([p.detach().reshape(-1).float() for p in model.G.parameters()])
+    idx = _fixed_sample(g.numel())
+    if idx is not None:
+      g = g[torch.from_numpy(idx).to(g.device)]
+    d = torch.cat([p.detach().reshape(-1).float() for p in model.D.parameters()])
+    bufs = torch.cat([b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()])
+    save_outputs(dirpath, [('losses', losses), ('fake_pose', ts.fake_pose), ('g_params_sample', g), ('d_params', d),
+                           ('bn_buffers', bufs)])
+
+
 def bench_inference(args):
   """configs[4]: the generator's eval forward (sample_flag=1: style ids given, BatchNorm from the running statistics folded into
   the prepared fp16 weights) on B=1024 clips, captured in a HIP graph; a step = one replay."""
@@ -550,6 +606,8 @@ def bench_inference(args):
       g.replay()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+  if args.dump_outputs:
+    save_outputs(args.dump_outputs, [('pose', y_cap)])
   fwd_gflop = (B_PER_GPU * T) / 2048.0 * 99.0
   ms = 1e3 * elapsed / args.steps
   out = {'metric': CONFIGS[args.config]['metric'], 'value': round(B_PER_GPU * args.steps / elapsed, 2), 'unit': 'clips/s', 'n_gpus': 1,
@@ -618,11 +676,15 @@ def main():
     wd.beat('warmup', 300)
   wd.beat('timed', 120)
   elapsed, kinds = time_steps(ts, batch, args.steps, None, world, dist, dev)
+  if args.dump_outputs and rank == 0:
+    wd.beat('dump', 300)
+    ts.check_health()
+    dump_train_outputs(args.dump_outputs, ts, model)
   wd.beat('per-kind', 120)
   losses = [float(l.detach()) for l in ts.losses]
   finite = all(l == l and abs(l) < 1e6 for l in losses)
   per_kind = None
-  if not args.no_per_kind:
+  if args.full and not args.no_per_kind:
     n_k = max(5, min(20, args.steps))
     per_kind = {}
     for kind in ('G', 'D'):
@@ -667,10 +729,10 @@ def main():
                              'mfma_frac_d_step': round(D_STEP_GFLOP / d_ms / peak, 4),
                              'note': 'per-rank algorithmic GFLOP of a whole step (G: 3 x 99.0, D: 99.0 + 6 x 0.215; SURVEY A.3) '
                                      '/ measured step time, against the matrix peak of the arithmetic mode (%.1f TF)' % peak})
-  if rank == 0 and world > 1:     # measured at N=1 only (per-kernel events / the CPU oracle would distort the ranks' lockstep)
+  if rank == 0 and world > 1 and args.full:     # measured at N=1 only (per-kernel events / the CPU oracle would distort the ranks' lockstep)
     out['roofline'] = None
     out['cpu_baseline'] = None
-  if rank == 0 and world == 1:
+  if rank == 0 and world == 1 and args.full:
     roof, rows = (None, [])
     if not args.no_kernel_timing:
       try:

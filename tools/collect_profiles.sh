@@ -11,17 +11,17 @@ cd "$R" && bash tools/pmc_chain.sh fp32 bf16 > "$OUT/pmc_decoder.log" 2>&1
 cp gpurun_out/pmc_decoder.json "$OUT/pmc_decoder.json"; cp gpurun_out/sq_counters.json "$OUT/sq_counters.json"
 cp gpurun_out/pmc_decoder.json profiles/${TAG}_pmc_decoder.json
 rm -rf gpurun_out/pmcchain
-cd "$R" && python bench.py > "$OUT/bench_full.log" 2>&1
+cd "$R" && python bench.py --full > "$OUT/bench_full.log" 2>&1
 grep -o '{"metric.*' "$OUT/bench_full.log" > "$OUT/bench.json"
-python bench.py --precision bf16 --no-cpu-baseline > "$OUT/bench_bf16_full.log" 2>&1
+python bench.py --full --precision bf16 --no-cpu-baseline > "$OUT/bench_bf16_full.log" 2>&1
 grep -o '{"metric.*' "$OUT/bench_bf16_full.log" > "$OUT/bench_bf16.json"
-python bench.py --precision bf16x6 --no-cpu-baseline --no-bf16-extra > "$OUT/bench_bf16x6_full.log" 2>&1
+python bench.py --full --precision bf16x6 --no-cpu-baseline --no-bf16-extra > "$OUT/bench_bf16x6_full.log" 2>&1
 grep -o '{"metric.*' "$OUT/bench_bf16x6_full.log" > "$OUT/bench_bf16x6.json"
 cd /tmp && export TMPDIR=/tmp
 # rocprofv3 per-kernel durations of the same commands (graph replay); the program comes directly after `--`
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$R/bench.py" --no-cpu-baseline --no-bf16-extra > "$OUT/stats_bench.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$R/bench.py" --full --no-cpu-baseline --no-bf16-extra > "$OUT/stats_bench.log" 2>&1
 cp "$OUT"/stats/*/*kernel_stats.csv "$OUT/kernel_stats.csv"; rm -rf "$OUT/stats"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats16" -- python3 "$R/bench.py" --precision bf16 --no-cpu-baseline > "$OUT/stats16_bench.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats16" -- python3 "$R/bench.py" --full --precision bf16 --no-cpu-baseline > "$OUT/stats16_bench.log" 2>&1
 cp "$OUT"/stats16/*/*kernel_stats.csv "$OUT/kernel_stats_bf16.csv"; rm -rf "$OUT/stats16"
 cd "$R"
 # what each kernel family costs inside the captured step (launches of a family dropped, step re-captured and re-timed)
@@ -29,7 +29,7 @@ python tools/ablate_step.py fp32 2>&1 | grep -v amdgpu.ids > "$OUT/ablation_fp32
 python tools/ablate_step.py bf16 2>&1 | grep -v amdgpu.ids > "$OUT/ablation_bf16.txt"
 # BASELINE configs[1], [3], [4] at their stated size and dtype (bench.py --config)
 for c in c2 c4 c5; do
-  python bench.py --config $c > "$OUT/bench_${c}_full.log" 2>&1
+  python bench.py --full --config $c > "$OUT/bench_${c}_full.log" 2>&1
   grep -o '{"metric.*' "$OUT/bench_${c}_full.log" > "$OUT/bench_$c.json"
 done
 # roofline-vs-size diagnostic: the same workload at B = 32 .. 256 clips per GPU (M = 8, T = 64), fp32 and bf16 (the chained launch

@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = {}
 for prec in ('fp32', 'bf16'):
   for B in (32, 64, 128, 256):
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--batch', str(B), '--precision', prec, '--steps', '10', '--warmup', '3',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--batch', str(B), '--precision', prec, '--steps', '10', '--warmup', '3',
            '--no-cpu-baseline', '--no-bf16-extra']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     line = [l for l in r.stdout.splitlines() if l.startswith('{')]

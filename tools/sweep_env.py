@@ -17,7 +17,7 @@ for r in range(rounds):
     if a != '-':
       for kv in a.split():
         k, v = kv.split('='); env[k] = v
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-bf16-extra',
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-bf16-extra',
                           '--precision', prec], env=env, capture_output=True, text=True)
     try:
       j = json.loads(out.stdout.strip().splitlines()[-1])
