@@ -219,7 +219,7 @@ int block_fwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
   if (fused) {
     a.ep = EP_BN_FUSED; a.out = y; a.out_raw = y_raw; a.bn_part = bn_part; a.bn_sync = bn_sync; a.save = save;
     a.momentum = d->momentum;
-    a.raw_all = (long)d->B * g.hw > BN_BWD16_FUSED_MAX;      // its two-pass backward reads y_raw, not y
+    a.raw_all = (long)d->B * g.hw > BN_BWD16_FUSED_MAX;      // its two-pass backward reads y_raw for the blocks y does not invert
   }
   const double esz = 2.0;
   const double flops = 2.0 * d->Cout * d->Cin * d->KH * d->KW * (double)g.npix * d->groups;

@@ -1405,7 +1405,7 @@ int launch_bn_finalize_apply(const float* stats, const float* counts, int n_tile
     const int want = (int)std::min<long>(B, std::max<long>(1, (per_item * B + 16383) / 16384));
     if (want > nchunk) { nchunk = want; bpc = cdiv(B, nchunk); nchunk = cdiv(B, bpc); }
   }
-  TimingScope ts(s, 0, 8.0 * (double)N * C, "bn_finalize_apply C%d N%d tiles%d", C, N, n_tiles);
+  TimingScope ts(s, 0, 8.0 * (double)N * C, "bn_finalize_apply<%d> C%d N%d tiles%d", vec ? 4 : 1, C, N, n_tiles);
   if (ts.skip()) return 0;
   if (vec)
     hipLaunchKernelGGL(bn_finalize_apply_kernel<4>, dim3(C, nchunk), dim3(256), 0, s, stats, counts, n_tiles, tile_n, N, C, gamma, beta, rm,
@@ -1444,9 +1444,11 @@ int launch_bn_bwd(const float* dy, const float* y_raw, const float* y, const flo
   const long n = (long)B * HW;
   if (sg > 1 && n > BN_BWD32_FUSED_MAX) return set_error("bn_bwd: statistics groups need the one-launch form (%ld values per channel)", n);
   if (n <= BN_BWD32_FUSED_MAX) {
-    TimingScope ts(s, 0, 12.0 * sg * B * C * HW, "bn_bwd_fused C%d HW%d B%d%s", C, HW, B * sg, sg > 1 ? " pair" : "");
-    if (ts.skip()) { *fused = 1; return 0; }
     const bool vec4 = (HW & 3) == 0 && (((uintptr_t)dy | (uintptr_t)y_raw | (uintptr_t)y | (uintptr_t)dyr) & 15) == 0;
+    // (the label names the kernel's form: "4" = the 16-byte kernel, <n> its template argument)
+    const int ne = vec4 ? (n <= 1024 ? 1 : n <= 2048 ? 2 : 4) : (n <= 256 * 4 ? 4 : n <= 256 * 8 ? 8 : 16);
+    TimingScope ts(s, 0, 12.0 * sg * B * C * HW, "bn_bwd_fused%s<%d> C%d HW%d B%d%s", vec4 ? "4" : "", ne, C, HW, B * sg, sg > 1 ? " pair" : "");
+    if (ts.skip()) { *fused = 1; return 0; }
     if (vec4 && n <= 1024)
       hipLaunchKernelGGL(bn_bwd_fused4_kernel<1>, dim3(C), dim3(256), 0, s, dy, y_raw, y, save, gamma, dyr, dbias, dgamma, dbeta, B, C, HW, slope, sg);
     else if (vec4 && n <= 2048)
@@ -1464,9 +1466,9 @@ int launch_bn_bwd(const float* dy, const float* y_raw, const float* y, const flo
   }
   int bpc;
   const int nchunk = bwd_chunks(B, C, &bpc);
-  TimingScope ts(s, 0, 20.0 * B * C * HW, "bn_bwd(reduce+apply) C%d HW%d B%d", C, HW, B);
-  if (ts.skip()) return 0;
   const bool vec = (HW & 3) == 0 && (((uintptr_t)dy | (uintptr_t)y_raw | (uintptr_t)dyr) & 15) == 0;
+  TimingScope ts(s, 0, 20.0 * B * C * HW, "bn_bwd(%s) C%d HW%d B%d", vec ? "reduce4+apply4" : "reduce+apply", C, HW, B);
+  if (ts.skip()) return 0;
   if (vec) hipLaunchKernelGGL(bn_bwd_reduce4_kernel, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, partial, colpart, B, C, HW, bpc, slope);
   else hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, partial, B, C, HW, bpc, slope);
   int rc = check_launch("bn_bwd_reduce_kernel");
@@ -1489,7 +1491,8 @@ int launch_act_bwd(const float* dy, const float* y, float* dyr, float* colpart, 
   *fused = 0;
   const long nn = (long)B * HW;
   if (nn <= 256 * 16 && (mode == 1 || dbias)) {
-    TimingScope ts(s, 0, (mode == 1 ? 12.0 : 4.0) * B * C * HW, "act_bwd_fused C%d HW%d B%d mode%d", C, HW, B, mode);
+    TimingScope ts(s, 0, (mode == 1 ? 12.0 : 4.0) * B * C * HW, "act_bwd_fused<%d> C%d HW%d B%d mode%d", nn <= 256 * 4 ? 4 : nn <= 256 * 8 ? 8 : 16,
+                   C, HW, B, mode);
     *fused = 1;
     if (ts.skip()) return 0;
     if (nn <= 256 * 4) hipLaunchKernelGGL(act_bwd_fused_kernel<4>, dim3(C), dim3(256), 0, s, dy, y, dyr, dbias, B, C, HW, mode, slope);

@@ -319,10 +319,13 @@ __device__ __forceinline__ bool bn_src_block(BnSrcShared& sh_, const float* __re
 }
 
 // BatchNorm + LeakyReLU backward, pass 1.  grid (C8, nchunk); chunk = contiguous range of batch items.
-//   dz = dy * lrelu'(z), z = y_raw*scale+shift;  xh = (y_raw-mean)*invstd;  partial[c][chunk] = (sum dz, sum dz*xh)
+//   dz = dy * lrelu'(z);  partial[c][chunk] = (sum dz, sum dz*xh).  z's sign and x_hat come from the block output y where the
+//   channel block inverts safely, else from y_raw (bn_src_block, as in the one-launch form): the sign of the ROUNDED y_raw is not
+//   the sign of the output the forward pass computed from its fp32 accumulators, and the gradient must be that output's
 template <typename DT, bool DYF32>
 __global__ __launch_bounds__(256) void bn_bwd16_reduce_kernel(const u32x4* __restrict__ dy, const float* __restrict__ dy_f32,
-                                                              const u32x4* __restrict__ y_raw, const float* __restrict__ save,
+                                                              const u32x4* __restrict__ y_raw, const u32x4* __restrict__ y_out,
+                                                              const float* __restrict__ save,
                                                               float* __restrict__ partial, float* __restrict__ xsum, int B, int C, int C8,
                                                               int HW, int b_per_chunk, float slope) {
   // xsum[c][chunk] = sum of x_hat: the bias gradient (a conv bias in front of BatchNorm: zero but for rounding) is
@@ -332,12 +335,9 @@ __global__ __launch_bounds__(256) void bn_bwd16_reduce_kernel(const u32x4* __res
   __shared__ float red[32];
   const int cb = blockIdx.x, ch = blockIdx.y, t = threadIdx.x, nchunk = gridDim.y;
   const int e_base = ch * b_per_chunk, b0 = 0;                   // chunk of the flattened (batch item, pixel) space
-  float mean[8], invstd[8], sc[8], sh[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = min(cb * 8 + j, C - 1);
-    mean[j] = save[c]; invstd[j] = save[C + c]; sc[j] = save[2 * C + c]; sh[j] = save[3 * C + c];
-  }
+  __shared__ BnSrcShared kshared;
+  BnSrc ks[8];
+  const u32x4* ysrc = bn_src_block(kshared, save, cb, C, slope, y_out != nullptr, ks) ? y_raw : y_out;
   float s1[8] = {}, s2[8] = {}, s3[8] = {};
   const int n = min(b_per_chunk, B * HW - e_base);
   // 4 vectors per thread and step, all loads issued before the first use
@@ -349,7 +349,7 @@ __global__ __launch_bounds__(256) void bn_bwd16_reduce_kernel(const u32x4* __res
       const int e = min(e0 + q * 256, n - 1);
       const int bl = fdHW.div(e_base + e), pix = e_base + e - bl * HW;
       const size_t b = b0 + bl, v = (b * C8 + cb) * HW + pix;
-      ry[q] = y_raw[v];
+      ry[q] = ysrc[v];
       if (DYF32) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) gf[q][j] = dy_f32[(b * C + min(cb * 8 + j, C - 1)) * HW + pix];
@@ -370,9 +370,9 @@ __global__ __launch_bounds__(256) void bn_bwd16_reduce_kernel(const u32x4* __res
         unpack8<DT>(ry[q], yr);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const float z = fmaf(yr[j], sc[j], sh[j]);
-          const float dz = g[j] * (z > 0.f ? 1.f : slope);
-          const float xh = (yr[j] - mean[j]) * invstd[j];
+          float xh; bool pos;
+          bn_xhat_mask(ks[j], yr[j], xh, pos);
+          const float dz = g[j] * (pos ? 1.f : slope);
           s1[j] += dz;
           s2[j] = fmaf(dz, xh, s2[j]);
           s3[j] += xh;
@@ -399,7 +399,8 @@ __global__ __launch_bounds__(256) void bn_bwd16_reduce_kernel(const u32x4* __res
 //   pass 2: dyr = gamma*invstd*(dz - s1/N - xh*s2/N); colsum partial of dyr; dgamma = s2, dbeta = s1
 template <typename DT, bool DYF32>
 __global__ __launch_bounds__(256) void bn_bwd16_apply_kernel(const u32x4* __restrict__ dy, const float* __restrict__ dy_f32,
-                                                             const u32x4* __restrict__ y_raw, const float* __restrict__ save,
+                                                             const u32x4* __restrict__ y_raw, const u32x4* __restrict__ y_out,
+                                                             const float* __restrict__ save,
                                                              const float* __restrict__ gamma, const float* __restrict__ partial,
                                                              u32x4* __restrict__ dyr, const float* __restrict__ xsum, float* dbias,
                                                              float* dgamma, float* dbeta, int B, int C, int C8, int HW, int b_per_chunk,
@@ -425,12 +426,13 @@ __global__ __launch_bounds__(256) void bn_bwd16_apply_kernel(const u32x4* __rest
     if (ii == 0) { prm[40 + jj] = a; prm[48 + jj] = b2; prm[56 + jj] = c3; }
     if (t < 40) prm[t] = pv;
   }
-  __syncthreads();
-  float mean[8], invstd[8], sc[8], sh[8], gi[8], m1[8], m2[8];
+  __shared__ BnSrcShared kshared;
+  BnSrc ks[8];
+  const u32x4* ysrc = bn_src_block(kshared, save, cb, C, slope, y_out != nullptr, ks) ? y_raw : y_out;     // (its barrier covers prm too)
+  float gi[8], m1[8], m2[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    mean[j] = prm[j]; invstd[j] = prm[8 + j]; sc[j] = prm[16 + j]; sh[j] = prm[24 + j];
-    gi[j] = cb * 8 + j < C ? prm[32 + j] * invstd[j] : 0.f;
+    gi[j] = cb * 8 + j < C ? prm[32 + j] * prm[8 + j] : 0.f;
     m1[j] = prm[40 + j] * invN; m2[j] = prm[48 + j] * invN;
   }
   if (t < 8 && ch == 0 && cb * 8 + t < C) {
@@ -450,7 +452,7 @@ __global__ __launch_bounds__(256) void bn_bwd16_apply_kernel(const u32x4* __rest
       const int bl = fdHW.div(e_base + e), pix = e_base + e - bl * HW;
       const size_t b = b0 + bl;
       vofs[q] = (b * C8 + cb) * HW + pix;
-      ry[q] = y_raw[vofs[q]];
+      ry[q] = ysrc[vofs[q]];
       if (DYF32) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) gf[q][j] = dy_f32[(b * C + min(cb * 8 + j, C - 1)) * HW + pix];
@@ -471,9 +473,9 @@ __global__ __launch_bounds__(256) void bn_bwd16_apply_kernel(const u32x4* __rest
         unpack8<DT>(ry[q], yr);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const float z = fmaf(yr[j], sc[j], sh[j]);
-          const float dz = g[j] * (z > 0.f ? 1.f : slope);
-          const float xh = (yr[j] - mean[j]) * invstd[j];
+          float xh; bool pos;
+          bn_xhat_mask(ks[j], yr[j], xh, pos);
+          const float dz = g[j] * (pos ? 1.f : slope);
           o[j] = gi[j] * (dz - m1[j] - xh * m2[j]);
         }
         dyr[vofs[q]] = pack8<DT>(o);
@@ -641,9 +643,10 @@ int launch_bn_bwd16(int dt, const void* dy, const float* dy_f32, const void* y_r
   if (ts.skip()) return 0;
 #define MS_BNB(DT, F)                                                                                                              \
   do {                                                                                                                             \
-    hipLaunchKernelGGL((bn_bwd16_reduce_kernel<DT, F>), grid, dim3(256), 0, s, (const u32x4*)dy, dy_f32, (const u32x4*)y_raw, save,   \
-                       partial, colpart, B, C, C8, HW, bpc, slope);                                                                \
-    hipLaunchKernelGGL((bn_bwd16_apply_kernel<DT, F>), grid, dim3(256), 0, s, (const u32x4*)dy, dy_f32, (const u32x4*)y_raw, save,    \
+    hipLaunchKernelGGL((bn_bwd16_reduce_kernel<DT, F>), grid, dim3(256), 0, s, (const u32x4*)dy, dy_f32, (const u32x4*)y_raw,         \
+                       (const u32x4*)y, save, partial, colpart, B, C, C8, HW, bpc, slope);                                         \
+    hipLaunchKernelGGL((bn_bwd16_apply_kernel<DT, F>), grid, dim3(256), 0, s, (const u32x4*)dy, dy_f32, (const u32x4*)y_raw,          \
+                       (const u32x4*)y, save,                                                                                      \
                        gamma, partial, (u32x4*)dyr, colpart, dbias, dgamma, dbeta, B, C, C8, HW, bpc, slope);                      \
   } while (0)
   if (dt == DT_BF16) { if (dy_f32) MS_BNB(BF16, true); else MS_BNB(BF16, false); }

@@ -18,7 +18,15 @@ def _round(t, dt):
 
 
 def _case(nd, B, cin, cout, groups, k, s, p, H, W, mode, in_mode=PLAIN, out_f32=False, dt=torch.bfloat16, seed=0, fragile=False,
-          slope=0.2, grad_tol=None):
+          slope=0.2, grad_tol=None, mask='exact', ref_dev='cpu', bn_folded=False, flip_frac=2e-3):
+  """One 16-bit block against fp64 on its rounded operands.  Returns {check: (measured, bar)}, values relative to the
+  reference's max-abs.
+
+  mask='device': the reference's LeakyReLU takes its slope from the sign of the device output.  Where the BatchNorm runs in a
+  launch of its own it normalises the STORED 16-bit conv output, so a pre-activation within one 16-bit rounding of 0 may take
+  the other slope than in exact math; such elements (at most `flip_frac` of the output, each within one rounding of the conv
+  output -- carried through BatchNorm's affine map -- of 0) follow the device, and every bar stays as it is.
+  ref_dev: where the float64 reference runs.  bn_folded: eval BatchNorm folded into the weights (the inference form)."""
   from mix_stage_amd import ops, ops16
   from mix_stage_amd._lib import MS_BF16, MS_F16
   msdt = MS_BF16 if dt == torch.bfloat16 else MS_F16
@@ -59,7 +67,7 @@ def _case(nd, B, cin, cout, groups, k, s, p, H, W, mode, in_mode=PLAIN, out_f32=
   if in_mode == UP2:
     y = ops16.conv_block16(xa, wp, bp, geom, mode, x2=xr, in_mode=UP2, **kw)
   else:
-    y = ops16.conv_block16(xc, wp, bp, geom, mode, in_mode=in_mode, **kw)
+    y = ops16.conv_block16(xc, wp, bp, geom, mode, in_mode=in_mode, bn_folded=bn_folded, **kw)
   ctot = cout * groups
   y32 = y if out_f32 else ops16.from_cb8(y, ctot)
   dyv = torch.randn(y32.shape, generator=g).to(DEV)
@@ -67,17 +75,18 @@ def _case(nd, B, cin, cout, groups, k, s, p, H, W, mode, in_mode=PLAIN, out_f32=
     (y32 * dyv).sum().backward()
 
   # ---- fp64 reference on the rounded operands
-  w64 = _round(w.cpu(), dt).requires_grad_()
-  b64 = bias.cpu().double().requires_grad_()
+  rdev = ref_dev
+  w64 = _round(w.to(rdev), dt).requires_grad_()
+  b64 = bias.to(rdev).double().requires_grad_()
   if in_mode == UP2:
-    a64, r64 = _round(a.detach().cpu(), dt), _round(r.detach().cpu(), dt)
+    a64, r64 = _round(a.detach().to(rdev), dt), _round(r.detach().to(rdev), dt)
     xin = _round((a64.repeat_interleave(2, dim=-1) + r64).float(), dt).requires_grad_()
   else:
-    xin = _round(x.detach().cpu(), dt).requires_grad_()
+    xin = _round(x.detach().to(rdev), dt).requires_grad_()
   xcat = torch.cat([xin] * groups, 1) if in_mode == BCAST else xin
   conv = F.conv2d if nd == 2 else F.conv1d
   raw = conv(xcat, w64, b64, stride=s, padding=p, groups=groups)
-  g64 = gamma.cpu().double().requires_grad_(); be64 = beta.cpu().double().requires_grad_()
+  g64 = gamma.to(rdev).double().requires_grad_(); be64 = beta.to(rdev).double().requires_grad_()
   dims = (0, 2, 3) if nd == 2 else (0, 2)
   shape = (1, -1, 1, 1) if nd == 2 else (1, -1, 1)
   if mode == BN_TRAIN:
@@ -87,35 +96,55 @@ def _case(nd, B, cin, cout, groups, k, s, p, H, W, mode, in_mode=PLAIN, out_f32=
     mean, var = raw.mean(dims), raw.var(dims, unbiased=False)
     raw_r = raw
     z = (raw_r - mean.view(shape)) / torch.sqrt(var.view(shape) + 1e-5) * g64.view(shape) + be64.view(shape)
+    zscale = g64.detach().abs() / torch.sqrt(var.detach() + 1e-5)
     ref = F.leaky_relu(z, slope)
   elif mode == BN_EVAL:
-    z = (raw - rm.cpu().double().view(shape)) / torch.sqrt(rv.cpu().double().view(shape) + 1e-5) * g64.view(shape) + be64.view(shape)
+    z = (raw - rm.to(rdev).double().view(shape)) / torch.sqrt(rv.to(rdev).double().view(shape) + 1e-5) * g64.view(shape) + be64.view(shape)
+    zscale = g64.detach().abs() / torch.sqrt(rv.to(rdev).double() + 1e-5)
     ref = F.leaky_relu(z, 0.2)
   elif mode == LRELU:
+    z, zscale = raw, torch.ones(ctot, dtype=torch.float64, device=raw.device)
     ref = F.leaky_relu(raw, 0.2)
   else:
     ref = raw
+  measured = {}      # (returned: check -> (measured, bar), relative to the reference's max-abs)
+  if mask == 'device' and mode != BARE:
+    pos = y32.detach().to(rdev) > 0
+    flip = pos != (z.detach() > 0)
+    u16 = 2.0 ** -8 if dt == torch.bfloat16 else 2.0 ** -11
+    zmax = z.detach().abs().max().item()
+    band = u16 * raw.detach().abs() * zscale.view(shape) + 1e-5 * zmax      # one rounding of the conv output, in units of z
+    outside = (flip & (z.detach().abs() > band)).sum().item()
+    frac = flip.sum().item() / flip.numel()
+    measured['mask flips (fraction)'] = (frac, flip_frac)
+    measured['mask flips beyond one rounding'] = (outside, 0)
+    assert outside == 0 and frac <= flip_frac, ('mask', flip.sum().item(), flip.numel(), outside)
+    sl = slope if mode == BN_TRAIN else 0.2
+    ref = torch.where(pos, z, sl * z)
   if mode != BN_EVAL:
-    dy_used = dyv.cpu().double() if out_f32 else _round(dyv.cpu(), dt)      # cb8 outputs receive a 16-bit gradient
+    dy_used = dyv.to(rdev).double() if out_f32 else _round(dyv.to(rdev), dt)      # cb8 outputs receive a 16-bit gradient
     (ref * dy_used).sum().backward()
 
   out_tol = 2e-5 if (out_f32 and mode != BN_TRAIN) else 1.2e-2      # fp32 from the accumulators vs one 16-bit rounding
   scale = ref.abs().max().item() + 1e-6
-  err = (y32.detach().cpu().double() - ref.detach()).abs().max().item()
+  err = (y32.detach().to(rdev).double() - ref.detach()).abs().max().item()
   assert err <= out_tol * scale, ('forward', err, scale)
+  measured['fwd'] = (err / scale, out_tol)
   if mode == BN_TRAIN:
     n = raw.numel() // ctot
-    new_rm = 0.9 * rm.cpu().double() + 0.1 * mean.detach()
-    new_rv = 0.9 * rv.cpu().double() + 0.1 * raw.detach().var(dims, unbiased=True) if n > 1 else None
-    assert (rm_h.cpu().double() - new_rm).abs().max().item() <= 1e-4
+    new_rm = 0.9 * rm.to(rdev).double() + 0.1 * mean.detach()
+    new_rv = 0.9 * rv.to(rdev).double() + 0.1 * raw.detach().var(dims, unbiased=True) if n > 1 else None
+    assert (rm_h.to(rdev).double() - new_rm).abs().max().item() <= 1e-4
     if new_rv is not None:
-      assert (rv_h.cpu().double() - new_rv).abs().max().item() <= 2e-3 * (1 + new_rv.abs().max().item())
+      assert (rv_h.to(rdev).double() - new_rv).abs().max().item() <= 2e-3 * (1 + new_rv.abs().max().item())
   # gradients: dy went through a 16-bit rounding (cb8 outputs) and BN backward rounds dy_raw again
   gt = grad_tol or (2e-2 if mode in (BN_TRAIN, LRELU) or not out_f32 else 1e-2)
   def close(a, b, what, tol=gt):
     sc = b.abs().max().item() + 1e-9
-    e = (a.detach().cpu().double() - b).abs().max().item()
-    l2 = (a.detach().cpu().double() - b).norm().item() / (b.norm().item() + 1e-12)
+    e = (a.detach().to(rdev).double() - b).abs().max().item()
+    l2 = (a.detach().to(rdev).double() - b).norm().item() / (b.norm().item() + 1e-12)
+    measured[what] = (e / sc, float('inf') if grad_tol else 2 * tol + 1e-6 / sc)
+    measured[what + ' l2'] = (l2, tol)
     # (a wrongly masked element -- y_raw path, |z| below one rounding -- is off by the LeakyReLU factor: bounded in l2, not in max)
     assert (grad_tol or e <= 2 * tol * sc + 1e-6) and l2 <= tol, (what, e, sc, l2)
   if mode != BN_EVAL:
@@ -130,6 +159,7 @@ def _case(nd, B, cin, cout, groups, k, s, p, H, W, mode, in_mode=PLAIN, out_f32=
       close(a.grad, dxin.reshape(dxin.shape[0], dxin.shape[1], -1, 2).sum(-1), 'dx')
     else:
       close(x.grad, xin.grad, 'dx')
+  return measured
 
 
 CASES_1D = [
