@@ -377,6 +377,33 @@ int ms_decoder_chain_sync_words(const ms_chain_desc* d);
 int ms_decoder_chain_prepare(const ms_chain_desc* d, const float* const* w, const float* w_logits, void* prepared, void* stream);
 int ms_decoder_chain_fwd(const ms_chain_desc* d, const ms_chain_tensors* t, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same unit for INFERENCE at any batch size and sequence length (MS_BN_EVAL only; MS_BN_TRAIN is refused): B >= 1, T >= 1,
+ * M <= 32, the other geometry as above (16-bit: cin0 in (264, 272], i.e. 34 channel blocks).  BatchNorm uses the running
+ * statistics (not written), so no workgroup of the launch waits for another one: no residency condition, no error word, any
+ * number of workgroups.  A sequence is cut into time tiles of 64 computed frames every 56 frames; a tile owns the frames at
+ * least 4 from its interior edges (four k3 / pad 1 blocks reach 4 frames), frames outside [0, T) are zero at the input of every
+ * block, as the reference's per-conv zero padding makes them.  A workgroup carries groups_per_workgroup sub-generators of one
+ * (sequence, tile) one after the other and accumulates the mixture; where that is fewer than M (few work units: the groups are
+ * spread so that the chip fills), each workgroup stores its partial sum in `workspace` and the one whose counter add came last
+ * sums them in ascending order -- a hand-off without a poll.  The plan, and with it the summation order, is a function of
+ * (B, T, M) alone: one shape, one result, bit for bit, eager or replayed from a graph.
+ *   tensors       ms_chain_tensors as above; y_raw, y, save are ignored (eval is not differentiated on the path); z and soft are
+ *                 optional; `prepared` is what ms_decoder_chain_prepare wrote (the streams depend on M, cin0, P, dtype only:
+ *                 ms_decoder_chain_prepare / _prepared_bytes accept a desc with any B and any T >= 1); blocks marked for BatchNorm
+ *                 folding are served from these unfolded streams, the scale applied in the fp32 epilogue.
+ *   sync          ms_decoder_chain_eval_sync_words zero-initialised int32 words from sync_first_word on, owned by one (device,
+ *                 stream) and one (B, T, M): monotonic counters, nothing to reset.  0 words (sync may be NULL) where one
+ *                 workgroup carries all M groups.
+ * _supported, _workspace, _sync_words and _plan are host arithmetic on the shape (no device needed).  _plan: n_tiles, the
+ * groups per workgroup, and per tile its first computed frame and its owned range [own_lo, own_hi) (arrays of `cap` >= n_tiles
+ * entries, or NULL). */
+int ms_decoder_chain_eval_supported(const ms_chain_desc* d);
+size_t ms_decoder_chain_eval_workspace(const ms_chain_desc* d);
+int ms_decoder_chain_eval_sync_words(const ms_chain_desc* d);
+int ms_decoder_chain_eval_plan(const ms_chain_desc* d, int32_t* n_tiles, int32_t* groups_per_workgroup, int32_t* tile_first,
+                               int32_t* own_lo, int32_t* own_hi, int32_t cap);
+int ms_decoder_chain_eval_fwd(const ms_chain_desc* d, const ms_chain_tensors* t, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Pre-step in front of the path ("next" row N1; src/data/transform.py, src/model/trainer.py:1290-1308), on device:
  * ms_kmeans_labels: KMeans.predict (transform.py:352-410) on RemoveJoints(pose): the feature blocks of KMeans.get_feats
  *   selected by `feats` (bit 0 pose (PK columns), bit 1 velocity (PK), bit 2 speed = |(vx, vy)| per kept joint (PK/2)), in

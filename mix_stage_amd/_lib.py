@@ -144,6 +144,11 @@ SIGNATURES = {
     'ms_decoder_chain_sync_words': (c_int, [_P]),
     'ms_decoder_chain_prepare': (c_int, [_P, _P, _P, _P, _P]),
     'ms_decoder_chain_fwd': (c_int, [_P, _P, _P, c_size_t, _P]),
+    'ms_decoder_chain_eval_supported': (c_int, [_P]),
+    'ms_decoder_chain_eval_workspace': (c_size_t, [_P]),
+    'ms_decoder_chain_eval_sync_words': (c_int, [_P]),
+    'ms_decoder_chain_eval_plan': (c_int, [_P, _P, _P, _P, _P, _P, c_int]),
+    'ms_decoder_chain_eval_fwd': (c_int, [_P, _P, _P, c_size_t, _P]),
     'ms_sqnorm': (c_int, [_P, c_size_t, _P, _P, _P]),
     'ms_adam_step': (c_int, [_P, _P, _P, _P, c_size_t, _P, c_float, c_float, c_float, c_float, c_float, _P, _P]),
     'ms_adam_step_segmented': (c_int, [_P, _P, _P, _P, c_size_t, _P, c_float, c_float, c_float, c_float, c_float, _P, _P, _P, _P,

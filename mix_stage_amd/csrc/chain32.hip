@@ -886,7 +886,10 @@ int ms_decoder_chain_sync_words(const ms_chain_desc* d) { return !d ? 0 : chain_
 int ms_decoder_chain_prepare(const ms_chain_desc* d, const float* const* w, const float* w_logits, void* prepared, void* stream) {
   if (!d || !w || !w_logits || !prepared) return set_error("ms_decoder_chain_prepare: null argument");
   for (int l = 0; l < CH_NL; ++l) if (!w[l]) return set_error("ms_decoder_chain_prepare: null weight");
-  return chain_is16(d) ? chain16_prepare(d, w, w_logits, prepared, (hipStream_t)stream) : chain32_prepare(d, w, w_logits, prepared, (hipStream_t)stream);
+  // the streams depend on M, cin0, P and the dtype only: any B and any T >= 1 (served by ms_decoder_chain_eval_fwd) prepare as T = 64 does
+  ms_chain_desc n = *d;
+  if (n.T >= 1) n.T = CH_T;
+  return chain_is16(&n) ? chain16_prepare(&n, w, w_logits, prepared, (hipStream_t)stream) : chain32_prepare(&n, w, w_logits, prepared, (hipStream_t)stream);
 }
 int ms_decoder_chain_fwd(const ms_chain_desc* d, const ms_chain_tensors* t, void* workspace, size_t workspace_bytes, void* stream) {
   if (!d || !t) return set_error("ms_decoder_chain_fwd: null argument");

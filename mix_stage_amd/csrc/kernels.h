@@ -215,6 +215,18 @@ size_t chain16_workspace(const ms_chain_desc* d);
 int chain16_sync_words(const ms_chain_desc* d);
 int chain16_prepare(const ms_chain_desc* d, const float* const* w, const float* wl, void* prepared, hipStream_t s);
 int chain16_fwd(const ms_chain_desc* d, const ms_chain_tensors* tn, void* workspace, size_t workspace_bytes, hipStream_t s);
+// ... and its wait-free eval form for any B and T (chain32_eval.hip, chain16_eval.hip), behind ms_decoder_chain_eval_*.
+// Time tiles of CHAIN_EVAL_TILE computed frames every CHAIN_EVAL_STEP frames; a tile owns what lies CHAIN_EVAL_HALO frames from
+// its interior edges.  CHAIN_EVAL_FILL: workgroups of one round (one per compute unit of the MI355X; the plan is a function of the
+// shape alone, it does not ask the device); CHAIN_EVAL_MAX_PARTS: partial-sum tiles (32 KB each) a launch may exchange.
+constexpr int CHAIN_EVAL_TILE = 64, CHAIN_EVAL_HALO = 4, CHAIN_EVAL_STEP = CHAIN_EVAL_TILE - 2 * CHAIN_EVAL_HALO, CHAIN_EVAL_FILL = 256,
+              CHAIN_EVAL_MAX_PARTS = 2048;
+struct ChainEvalPlan { int n_tiles, gpw, ngw; long units; };   // gpw groups per workgroup, ngw workgroups per unit, units = B * n_tiles
+ChainEvalPlan chain_eval_plan(const ms_chain_desc* d);
+int chain_eval_shape_ok(const ms_chain_desc* d);
+size_t chain_eval_workspace(const ms_chain_desc* d);
+int chain_eval_sync_words(const ms_chain_desc* d);
+int chain16_eval_fwd(const ms_chain_desc* d, const ms_chain_tensors* tn, void* workspace, size_t workspace_bytes, hipStream_t s);
 
 struct GatherPlan { int tm, tn, splitk, k_per_split, n_tiles; };
 // tile shape + split-K factor for an (Mg x npix) output per z-slice (z = groups * parity classes), reduction Kg

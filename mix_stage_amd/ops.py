@@ -772,6 +772,9 @@ def sync_bn_act(y_raw, gamma, beta, running_mean, running_var, slope, eps, momen
 # Chained pose decoder (include/mixstage.h: ms_decoder_chain_fwd): decoder.0-3 + logits + softmax mixture in one launch.
 CHAIN_SYNC_FIRST_WORD = 32             # (word 0 of the chain's sync buffer is the error flag: ops16.chain_sync)
 USE_DECODER_CHAIN = os.environ.get('MS_DECODER_CHAIN', '1') != '0'       # ablations: MS_DECODER_CHAIN=0 runs the blocks one by one
+# the wait-free eval form (ms_decoder_chain_eval_fwd) for the eval shapes the launch above cannot take: any B, any T.
+# A/B runs: MS_CHAIN_EVAL=0 keeps those shapes on the blocks one by one
+USE_DECODER_CHAIN_EVAL = os.environ.get('MS_CHAIN_EVAL', '1') != '0'
 
 
 def _chain_desc(B, M, T, cin0, P, mode, blk, dtype=0):
@@ -809,16 +812,53 @@ def _chain_prepared(d, ws):
   return e['wt']
 
 
+_chain_eval_sync = {}
+
+
+def _chain_eval_launch(d, x, score, blocks, logits, ws, P):
+  """The eval form of the chained decoder for desc d (MS_BN_EVAL, no gradient): (out (B,T,P), soft (B,T,M)), or None where
+  ms_decoder_chain_eval_supported declines.  It waits for no other workgroup, so it does not depend on in-launch meetings being
+  allowed; its counters (where the plan spreads the groups of a tile over workgroups) are monotonic words of their own per
+  (device, stream, shape)."""
+  if not USE_DECODER_CHAIN_EVAL or not lib().ms_decoder_chain_eval_supported(ctypes.byref(d)):
+    return None
+  dev = x.device
+  prepared = _chain_prepared(d, ws)
+  words = lib().ms_decoder_chain_eval_sync_words(ctypes.byref(d))
+  sync = None
+  if words:
+    key = (dev.type, dev.index, torch.cuda.current_stream(dev).cuda_stream, d.B, d.M, d.T)
+    sync = _chain_eval_sync.get(key)
+    if sync is None or sync.numel() < CHAIN_SYNC_FIRST_WORD + words:
+      sync = _chain_eval_sync[key] = torch.zeros(CHAIN_SYNC_FIRST_WORD + words, dtype=torch.int32, device=dev)
+  soft = torch.empty((d.B, d.T, d.M), dtype=torch.float32, device=dev)
+  out = torch.empty((d.B, d.T, P), dtype=torch.float32, device=dev)
+  tn = _lib.ChainTensors()
+  tn.x, tn.score = x.data_ptr(), score.data_ptr()
+  for l, m in enumerate(blocks):
+    tn.w[l], tn.bias[l] = m.conv.weight.data_ptr(), (m.conv.bias.data_ptr() if m.conv.bias is not None else None)
+    tn.gamma[l], tn.beta[l] = m.norm.weight.data_ptr(), m.norm.bias.data_ptr()
+    tn.running_mean[l], tn.running_var[l] = m.norm.running_mean.data_ptr(), m.norm.running_var.data_ptr()
+  tn.w_logits, tn.bias_logits = logits.weight.data_ptr(), logits.bias.data_ptr()
+  tn.soft, tn.out, tn.prepared = soft.data_ptr(), out.data_ptr(), prepared.data_ptr()
+  if sync is not None:
+    tn.sync, tn.sync_words = sync.data_ptr(), sync.numel()
+  wsp = workspace(lib().ms_decoder_chain_eval_workspace(ctypes.byref(d)), dev)
+  check(lib().ms_decoder_chain_eval_fwd(ctypes.byref(d), ctypes.byref(tn), _ptr(wsp), wsp.numel(), _stream()), 'ms_decoder_chain_eval_fwd')
+  return out, soft
+
+
 def decoder_chain(x, blocks, logits, score, P):
   """(out (B,T,P), soft (B,T,M)) = softmax mixture of logits(decoder(x)) for the M sub-generators (JL:190-194) in ONE launch, or
-  None when this shape / mode / device is not served by the chained kernel (the caller then runs the blocks one by one).
+  None when this shape / mode / device is not served by a chained kernel (the caller then runs the blocks one by one).  Train
+  mode and eval at T = 64 with B*M <= compute units: ms_decoder_chain_fwd (its workgroups meet inside the launch); eval without
+  gradients at any other B / T: the wait-free ms_decoder_chain_eval_fwd (_chain_eval_launch).
   blocks: the four ConvNormRelu modules of the grouped decoder; logits: the grouped 1x1 nn.Conv1d; x (B, cin0, T) fp32 shared by
   all groups; score (B, M, T)."""
-  if not USE_DECODER_CHAIN or len(blocks) != 4 or x.dim() != 3 or not x.is_cuda or x.dtype != torch.float32 or bn_sync_active():
+  if not USE_DECODER_CHAIN or len(blocks) != 4 or x.dim() != 3 or not x.is_cuda or x.dtype != torch.float32:
     return None
   from . import ops16
-  if not ops16.in_launch_meetings():
-    return None
+  meetings = ops16.in_launch_meetings() and not bn_sync_active()       # (the one-launch form meets inside the launch)
   blk0 = blocks[0]
   M = blk0.conv.groups
   B, cin0, T = x.shape
@@ -844,12 +884,19 @@ def decoder_chain(x, blocks, logits, score, P):
   if need_grad and not training:
     return None                            # (eval-mode blocks are never differentiated on the path)
   d = _chain_desc(B, M, T, cin0, P, mode, blk0)
+  ws = [m.conv.weight for m in blocks] + [logits.weight]
   if not lib().ms_decoder_chain_supported(ctypes.byref(d)):
-    return None
+    # not a shape of the one-launch form (T != 64, or more workgroups than can be resident at once): inference has the wait-free
+    # eval form, whatever the state of the meetings; train mode runs the blocks one by one
+    if training or need_grad:
+      return None
+    _need_hip(x, score, *[t for t in params if t is not None])
+    return _chain_eval_launch(d, x.contiguous(), score.contiguous(), blocks, logits, ws, P)
+  if not meetings:
+    return None                            # (a shape of the one-launch form while meetings are off: the blocks one by one, as ever)
   _need_hip(x, score, *[t for t in params if t is not None])
   x, score = x.contiguous(), score.contiguous()
   dev = x.device
-  ws = [m.conv.weight for m in blocks] + [logits.weight]
   prepared = _chain_prepared(d, ws)
   sync = ops16.chain_sync(dev, B, M, CHAIN_SYNC_FIRST_WORD + lib().ms_decoder_chain_sync_words(ctypes.byref(d)))
   C = 256 * M

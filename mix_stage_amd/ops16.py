@@ -381,8 +381,9 @@ def conv_block16(x, w, bias, geom, mode, gamma=None, beta=None, running_mean=Non
 # ------------------------------------------------------------------------------------------------
 def decoder_chain16(x, blocks, logits, score, P):
   """16-bit form of ops.decoder_chain: x cb8 (B, 34, T, 8) shared by all groups; (out (B,T,P) fp32, soft (B,T,M)) or None."""
-  if not ops.USE_DECODER_CHAIN or len(blocks) != 4 or not is_cb8(x) or x.dim() != 4 or ops.bn_sync_active() or not in_launch_meetings():
+  if not ops.USE_DECODER_CHAIN or len(blocks) != 4 or not is_cb8(x) or x.dim() != 4:
     return None
+  meetings = in_launch_meetings() and not ops.bn_sync_active()         # (the one-launch form meets inside the launch)
   dt = MS_DT[x.dtype]
   blk0 = blocks[0]
   M = blk0.conv.groups
@@ -392,8 +393,7 @@ def decoder_chain16(x, blocks, logits, score, P):
     return None
   if any(getattr(m, '_ms_dt', 0) != dt for m in blocks) or getattr(logits, '_ms_dt', 0) != dt or any(m._p and m.training for m in blocks):
     return None
-  if any(getattr(m, '_bn_folded', False) for m in blocks):
-    return None
+  folded = any(getattr(m, '_bn_folded', False) for m in blocks)
   if any(m._forward_hooks or m._forward_pre_hooks for m in list(blocks) + [logits]):
     return None
   if any(m.conv.groups != M or m.conv.kernel_size != (3,) or m.conv.stride != (1,) or m.conv.padding != (1,) or
@@ -414,12 +414,19 @@ def decoder_chain16(x, blocks, logits, score, P):
   if need_grad and not training:
     return None
   d = ops._chain_desc(B, M, T, cin0, P, mode, blk0, dt)
+  wts = [m.conv.weight for m in blocks] + [logits.weight]
   if not lib().ms_decoder_chain_supported(ctypes.byref(d)):
+    # inference outside the one-launch form's shapes: the wait-free eval form (ops.decoder_chain).  Blocks marked for BatchNorm
+    # folding are served from the unfolded streams, the scale applied in the fp32 epilogue
+    if training or need_grad:
+      return None
+    _need16(x, score, *[t for t in params if t is not None])
+    return ops._chain_eval_launch(d, x.contiguous(), score.contiguous(), blocks, logits, wts, P)
+  if folded or not meetings:
     return None
   _need16(x, score, *[t for t in params if t is not None])
   x, score = x.contiguous(), score.contiguous()
   dev = x.device
-  wts = [m.conv.weight for m in blocks] + [logits.weight]
   prepared = ops._chain_prepared(d, wts)
   sync = chain_sync(dev, B, M, ops.CHAIN_SYNC_FIRST_WORD + lib().ms_decoder_chain_sync_words(ctypes.byref(d)))
   C = 256 * M

@@ -7,6 +7,9 @@ fully-convolutional model once per target style with sample_flag=1, eval-mode Ba
 
 Here the eval forward (running-statistics BatchNorm is folded into each conv kernel's epilogue, MS_BN_EVAL) is captured
 into one HIP graph per sequence length and replayed for every target style; inputs live in static HBM buffers.
+The pose decoder of such a long sequence (T = n*64, never 64) runs as the wait-free eval form of the chained decoder
+(ops.decoder_chain -> ms_decoder_chain_eval_fwd: time tiles of 64 frames, activations resident in LDS through the four
+blocks, no workgroup waiting for another one); MS_CHAIN_EVAL=0 keeps it on the blocks one by one.
 Dataset I/O, ground-truth loading, metrics and rendering around the loop stay out of scope.
 """
 import torch
@@ -70,7 +73,7 @@ class StyleTransferSampler:
       results.append((name, entry['y_cap'].clone(), [l.clone() for l in entry['losses']]))
     # an in-launch meeting that gave up (the launch did not have the GPU to itself) poisons its outputs with NaN: outside a
     # training step nobody else looks at the error word, so every interval ends with the (synchronising) check -- the caller is
-    # about to read the poses anyway
+    # about to read the poses anyway.  (The decoder's eval form meets nobody; other kernels of the forward still do.)
     from . import ops16
     ops16.check_meetings()
     return results
