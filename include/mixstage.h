@@ -288,6 +288,7 @@ int ms_wgrad_reduce_multi(int n, const float* const* partials, float* const* dw,
  *   ms_bn_train_apply  stats_all[world][C][2] (all-gathered, n_local = B*HW values each) -> save = mean|invstd|scale|shift of
  *                      the GLOBAL batch, running statistics update (global count), y = lrelu(y_raw*scale + shift)
  *   ms_bn_bwd_sums     sums[C][2] = this rank's (sum dz, sum dz*xhat), dz = dy*lrelu'(z): also its dbeta / dgamma
+ *                      (summed in double; workspace of ms_bn_bwd_workspace(B, C) bytes, 8-byte aligned)
  *   ms_bn_bwd_apply    dyr = gamma*invstd*(dz - S1/N - xhat*S2/N) with the all-reduced sums S and the global count N */
 int ms_bn_stats(const float* y_raw, float* stats, int B, int C, int HW, void* stream);
 int ms_bn_train_apply(const float* stats_all, int world, int n_local, const float* gamma, const float* beta, float* running_mean,

@@ -207,16 +207,50 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
   if (t == 0) { out[2 * c] = s; out[2 * c + 1] = q; }
 }
 
-// sums the per-chunk partials of bn_bwd_reduce_kernel: sums[c] = (sum dz, sum dz*xhat) of this rank
-__global__ void bn_bwd_sum_chunks_kernel(const float* __restrict__ partial, float* __restrict__ sums, int C, int nchunk) {
+// The stand-alone sums of the cross-rank BatchNorm (ms_bn_bwd_sums): (sum dz, sum dz*xhat) of this rank per channel, in two stages like
+// bn_bwd_reduce_kernel (grid (C, nchunk), chunk = contiguous range of batch items) but with the terms and every partial sum in double.
+// sum dz*xhat cancels (about sqrt(n) of n terms of size 1 remain): with fp32 terms and fp32 partials a single channel of 2047 values
+// came out 9e-7 off, more than four times what an fp32 evaluation on the host loses.  The activation mask still comes from the fp32
+// z = fma(y_raw, scale, shift), bit-identical to the forward pass.
+__global__ __launch_bounds__(256) void bn_bwd_reduce_wide_kernel(const float* __restrict__ dy, const float* __restrict__ y_raw,
+                                                                 const float* __restrict__ save, double* __restrict__ partial, int B,
+                                                                 int C, int HW, int b_per_chunk, float slope) {
+  __shared__ double red[8];
+  const int c = blockIdx.x, ch = blockIdx.y, t = threadIdx.x;
+  const int b0 = ch * b_per_chunk, nb = min(b_per_chunk, B - b0);
+  const float sc = save[2 * C + c], sh = save[3 * C + c];
+  const double mean = (double)save[c], invstd = (double)save[C + c];
+  double s1 = 0.0, s2 = 0.0;
+  const int n = nb * HW;
+  for (int e = t; e < n; e += 256) {
+    const int b = b0 + e / HW, pix = e % HW;
+    const size_t off = ((size_t)b * C + c) * HW + pix;
+    const float yr = y_raw[off];
+    const float z = fmaf(yr, sc, sh);
+    const double dz = (double)dy[off] * (z > 0.f ? 1.0 : (double)slope);
+    s1 += dz;
+    s2 += dz * (((double)yr - mean) * invstd);
+  }
+  s1 = wave_sum_d(s1);
+  s2 = wave_sum_d(s2);
+  if ((t & 63) == 0) { red[t >> 6] = s1; red[4 + (t >> 6)] = s2; }
+  __syncthreads();
+  if (t == 0) {
+    partial[((size_t)c * gridDim.y + ch) * 2] = (red[0] + red[1]) + (red[2] + red[3]);
+    partial[((size_t)c * gridDim.y + ch) * 2 + 1] = (red[4] + red[5]) + (red[6] + red[7]);
+  }
+}
+
+// sums the per-chunk partials of bn_bwd_reduce_wide_kernel (up to 1024 per channel when C = 1, added by one thread)
+__global__ void bn_bwd_sum_chunks_kernel(const double* __restrict__ partial, float* __restrict__ sums, int C, int nchunk) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  float s1 = 0.f, s2 = 0.f;
+  double s1 = 0.0, s2 = 0.0;
   for (int k = 0; k < nchunk; ++k) {
     s1 += partial[((size_t)c * nchunk + k) * 2];
     s2 += partial[((size_t)c * nchunk + k) * 2 + 1];
   }
-  sums[2 * c] = s1; sums[2 * c + 1] = s2;
+  sums[2 * c] = (float)s1; sums[2 * c + 1] = (float)s2;
 }
 
 // dyr = gamma*invstd*(dz - S1/N - xhat*S2/N) with the GLOBAL sums S and the global count N
@@ -1317,11 +1351,14 @@ __global__ __launch_bounds__(256) void adam_seg_kernel(float* __restrict__ p, co
   // 16 bytes per lane and stream, two vectors per thread in flight (7 streams over the 60 MB of live parameters: dword accesses
   // ran at 5.4 TB/s); a 64-element chunk belongs to one segment, so a vector does too.  n is a multiple of 64 (FlatAdam's layout);
   // the buffers are 256-byte aligned
+  // the roundings are spelled out (explicit fma, contraction off): the vector path and the scalar fallback below give the same bits
+  // for the same element -- left to the compiler, the fallback rounded the products of mn and vn separately and the vector path did not
   auto upd = [&](float pi, float gr, float mo, float vo, float step_size, float bc2s, float& mn, float& vn) {
+#pragma clang fp contract(off)
     const float gi = gr * coef;
-    mn = mo + (1.f - beta1) * (gi - mo);
-    vn = beta2 * vo + (1.f - beta2) * gi * gi;
-    return pi - step_size * (mn / (sqrtf(vn) / bc2s + eps));
+    mn = fmaf(1.f - beta1, fmaf(gr, coef, -mo), mo);
+    vn = fmaf(beta2, vo, gi * ((1.f - beta2) * gi));
+    return fmaf(-step_size, mn / (sqrtf(vn) / bc2s + eps), pi);
   };
   if ((n & 3) == 0 && ((((size_t)p | (size_t)g | (size_t)m | (size_t)v) & 15) == 0)) {
     const size_t n4 = n >> 2, stride = (size_t)gridDim.x * 256;
@@ -1591,7 +1628,7 @@ int ms_bn_train_apply(const float* stats_all, int world, int n_local, const floa
 
 size_t ms_bn_bwd_workspace(int B, int C) {
   int bpc;
-  return (size_t)bwd_chunks(B, C, &bpc) * C * 2 * sizeof(float) + 256;
+  return (size_t)bwd_chunks(B, C, &bpc) * C * 2 * sizeof(double) + 256;        // double partials (bn_bwd_reduce_wide_kernel)
 }
 
 int ms_bn_bwd_sums(const float* dy, const float* y_raw, const float* save, float* sums, int B, int C, int HW, float slope,
@@ -1602,8 +1639,9 @@ int ms_bn_bwd_sums(const float* dy, const float* y_raw, const float* save, float
   int bpc;
   const int nchunk = bwd_chunks(B, C, &bpc);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, (float*)workspace, B, C, HW, bpc, slope);
-  hipLaunchKernelGGL(bn_bwd_sum_chunks_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, (const float*)workspace, sums, C, nchunk);
+  if ((size_t)workspace & 7) return set_error("ms_bn_bwd_sums: the workspace must be 8-byte aligned");
+  hipLaunchKernelGGL(bn_bwd_reduce_wide_kernel, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, (double*)workspace, B, C, HW, bpc, slope);
+  hipLaunchKernelGGL(bn_bwd_sum_chunks_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, (const double*)workspace, sums, C, nchunk);
   return check_launch("bn_bwd_sums kernels");
 }
 

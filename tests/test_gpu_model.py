@@ -77,9 +77,18 @@ def _compare_step(M, S, B, kind, F_, seed, strict):
   rec_r, h_r = _record_block_outputs(ref, lambda m: isinstance(m, O.ConvNormRelu))
   rec_h, h_h = _record_block_outputs(hip, lambda m: isinstance(m, A.ConvNormRelu))
   batch64 = [t.double() if t.is_floating_point() else t for t in batch]
+  pse = {}
+
+  def _pse_hook(k):
+    def hook(mod, i, o):
+      pse.setdefault(k, o.detach().cpu().double())          # the first call of a step: the scores of the ground-truth pose
+    return hook
+  h_pse = [m.G.pose_style_encoder.register_forward_hook(_pse_hook(k)) for k, m in (('ref', ref), ('hip', hip))]
   f_ref, l_ref = _step(ref, batch64, kind, 'cpu')
   f_hip, l_hip = _step(hip, batch, kind, DEV)
   for h in h_r + h_h:
+    h.remove()
+  for h in h_pse:
     h.remove()
   flips = _count_kink_flips(rec_h, rec_r)
   l1 = (f_hip.detach().cpu().double() - f_ref.detach()).abs().mean().item()
@@ -88,6 +97,11 @@ def _compare_step(M, S, B, kind, F_, seed, strict):
     assert abs(float(a) - float(b)) <= 1e-4, (float(a), float(b))
   assert (hip.G.labels_cap_soft.cpu().double() - ref.G.labels_cap_soft.detach()).abs().max().item() <= 1e-4
   assert hip.G_flag == ref.G_flag
+  # the style-id argmax of the pose style encoder: bit-exact (the fp64 top-2 margin is reported with a mismatch)
+  assert set(pse) == {'ref', 'hip'} and pse['hip'].shape == pse['ref'].shape
+  top2 = pse['ref'].topk(2, dim=-1).values
+  assert torch.equal(pse['hip'].argmax(-1), pse['ref'].argmax(-1)), \
+      'style-id argmax differs from the oracle; smallest fp64 top-2 margin %.3g' % (top2[..., 0] - top2[..., 1]).min().item()
   if strict and flips:
     return flips
   # flip-free: every element within 2e-3 of the parameter's max |grad|.  With flips (a handful of activations out of
