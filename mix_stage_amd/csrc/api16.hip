@@ -1,45 +1,24 @@
 // 16-bit arithmetic mode (desc.dtype = MS_BF16 / MS_F16): one conv block forward / backward on cb8 tensors, reached from the
 // ms_conv_block_* entry points of api.hip, plus the batched weight preparation (ms_weights16_prepare).
-#include <algorithm>
-
-#include "conv16.h"
+#include "block_geom.h"
 
 namespace ms {
 
 namespace {
 
-struct Geo16 {
-  int dt, nd, C, C8, cin_tot, cin8_tot, npix, hw, up2, bcast, one_d;
-};
-Geo16 geo_of(const ms_conv_desc* d) {
-  Geo16 g;
-  g.dt = dt_of(d);
-  g.one_d = d->H == 1 && d->KH == 1;
-  g.nd = g.one_d ? 1 : 2;
-  g.C = d->groups * d->Cout; g.C8 = c8_of(g.C);
-  g.bcast = d->in_mode == MS_IN_BCAST; g.up2 = d->in_mode == MS_IN_UP2ADD;
-  g.cin_tot = g.bcast ? d->Cin : d->groups * d->Cin; g.cin8_tot = c8_of(g.cin_tot);
-  g.npix = d->B * d->OH * d->OW; g.hw = d->OH * d->OW;
-  return g;
-}
-
 Conv16Plan fwd_plan16(const ms_conv_desc* d) {
-  const Geo16 g = geo_of(d);
+  const BlockGeo g = geo_of(d);
   return plan_conv16(g.nd, d->Cout, d->groups, d->Cin, d->KH, d->KW, d->SH, d->SW, d->B, d->OH, d->OW, 1, g.up2 != 0);
 }
-struct Dgrad16 { int tg, tcog, jh, jw, ncls; Conv16Plan pl; };
+struct Dgrad16 : DgradGeo { Conv16Plan pl; };
 Dgrad16 dgrad_plan16(const ms_conv_desc* d) {
-  const Geo16 g = geo_of(d);
   Dgrad16 r;
-  r.tg = g.bcast ? 1 : d->groups;
-  r.tcog = g.bcast ? g.C : d->Cout;
-  r.jh = cdiv(d->KH, d->SH); r.jw = cdiv(d->KW, d->SW);
-  r.ncls = d->SH * d->SW;
-  r.pl = plan_conv16(g.nd, d->Cin, r.tg, r.tcog, r.jh, r.jw, 1, 1, d->B, cdiv(d->H, d->SH), cdiv(d->W, d->SW), r.ncls, false);
+  static_cast<DgradGeo&>(r) = dgrad_geo_of(d);
+  r.pl = plan_conv16(geo_of(d).nd, d->Cin, r.tg, r.tcog, r.jh, r.jw, 1, 1, d->B, cdiv(d->H, d->SH), cdiv(d->W, d->SW), r.ncls, false);
   return r;
 }
 Wgrad16Plan wgrad_plan16(const ms_conv_desc* d) {
-  const Geo16 g = geo_of(d);
+  const BlockGeo g = geo_of(d);
   return plan_wgrad16(g.nd, d->Cout, d->Cin, d->groups, d->KH, d->KW, d->SH, d->SW, d->B, d->OH, d->OW, g.up2 != 0);
 }
 size_t fwd_a_bytes(const ms_conv_desc* d, const Conv16Plan& pl) {
@@ -89,30 +68,45 @@ int wgrad16_splits(const ms_conv_desc* d) {
   return wp.tp ? wp.splits : 1;
 }
 
-size_t block_fwd16_workspace(const ms_conv_desc* d) {
-  const Geo16 g = geo_of(d);
-  const Conv16Plan pl = fwd_plan16(d);
-  size_t bytes = 256;
+namespace {
+
+// Scratch of the forward, byte offsets, regions in this order: tile statistics | tile counts | partials of the in-launch BatchNorm
+// (BN_TRAIN) | per-call weight preparation: the A operand (a whole ms_weights16_bytes buffer) | folded scale, bias'
+struct Fwd16Layout { size_t stats, counts, bn_part, A, fold, total; };
+Fwd16Layout fwd16_layout(const ms_conv_desc* d, const Conv16Plan& pl) {
+  Fwd16Layout l = {};
   if (pl.ok) {
-    bytes += align_up((size_t)pl.n_tiles * g.C * 2 * sizeof(float), 256) + align_up((size_t)pl.n_tiles * sizeof(float), 256);
-    if (d->mode == MS_BN_TRAIN) bytes += bn_part_bytes(d, pl);
-    bytes += weights16_bytes(d, 0) + align_up((size_t)2 * g.C * sizeof(float), 256);   // per-call weight preparation
+    const int C = d->groups * d->Cout;
+    l.stats = carve(l.total, align_up((size_t)pl.n_tiles * C * 2 * sizeof(float), 256));
+    l.counts = carve(l.total, align_up((size_t)pl.n_tiles * sizeof(float), 256));
+    l.bn_part = carve(l.total, d->mode == MS_BN_TRAIN ? bn_part_bytes(d, pl) : 0);
+    l.A = carve(l.total, weights16_bytes(d, 0));
+    l.fold = carve(l.total, align_up((size_t)2 * C * sizeof(float), 256));
   }
-  return bytes;
+  l.total += 256;
+  return l;
 }
 
-size_t block_bwd16_workspace(const ms_conv_desc* d) {
-  const Geo16 g = geo_of(d);
+// ... and of the backward: BatchNorm partials | column sums | per-call data-gradient operand | weight-gradient slabs (splits > 1)
+struct Bwd16Layout { size_t bn_part, colpart, wt, wg_part, total; int nchunk; };
+Bwd16Layout bwd16_layout(const ms_conv_desc* d) {
+  const BlockGeo g = geo_of(d);
+  Bwd16Layout l = {};
   int bpc;
-  const int nchunk = bwd16_chunks(d->B, g.C8, g.hw, &bpc);
-  size_t bytes = 256;
-  bytes += align_up((size_t)g.C8 * 8 * nchunk * 2 * sizeof(float), 256);
-  bytes += align_up((size_t)g.C8 * 8 * nchunk * sizeof(float), 256);
-  bytes += weights16_bytes(d, 1);
+  l.nchunk = bwd16_chunks(d->B, g.C8, g.hw, &bpc);
+  l.bn_part = carve(l.total, align_up((size_t)g.C8 * 8 * l.nchunk * 2 * sizeof(float), 256));
+  l.colpart = carve(l.total, align_up((size_t)g.C8 * 8 * l.nchunk * sizeof(float), 256));
+  l.wt = carve(l.total, weights16_bytes(d, 1));
   const int sp = wgrad16_splits(d);
-  if (sp > 1) bytes += align_up((size_t)sp * g.C * d->Cin * d->KH * d->KW * sizeof(float), 256);
-  return bytes;
+  l.wg_part = carve(l.total, sp > 1 ? align_up((size_t)sp * wsize_of(d) * sizeof(float), 256) : 0);
+  l.total += 256;
+  return l;
 }
+
+}  // namespace
+
+size_t block_fwd16_workspace(const ms_conv_desc* d) { return fwd16_layout(d, fwd_plan16(d)).total; }
+size_t block_bwd16_workspace(const ms_conv_desc* d) { return bwd16_layout(d).total; }
 
 // MS_DT_STAT_PAIR in the 16-bit modes: the conv leaves its tile statistics (EP_RAW_STATS) and the normalising launch combines them
 // per half of the batch (bn_finalize_apply16_kernel) -- needs whole statistics tiles per half, at most 32 of them, a cb8 output,
@@ -120,7 +114,7 @@ size_t block_bwd16_workspace(const ms_conv_desc* d) {
 bool stat_pair16_ok(const ms_conv_desc* d) {
   if (d->mode != MS_BN_TRAIN) return true;
   if ((d->B & 1) || out_f32_of(d)) return false;
-  const Geo16 g = geo_of(d);
+  const BlockGeo g = geo_of(d);
   const Conv16Plan pl = fwd_plan16(d);
   if (!pl.ok || (pl.n_tiles & 1) || pl.n_tiles > 64) return false;
   if (g.one_d && ((d->B / 2) % pl.th)) return false;          // (1-D: the batch is the row axis of one image; 2-D: tiles per image)
@@ -130,7 +124,7 @@ bool stat_pair16_ok(const ms_conv_desc* d) {
 int block_fwd16(const ms_conv_desc* d, const void* x, const void* x2, const float* w, const float* bias, const float* gamma,
                 const float* beta, float* running_mean, float* running_var, void* y_raw, void* y, float* save, void* workspace,
                 size_t workspace_bytes, hipStream_t s, const void* w_prepared, int32_t* bn_sync, int bn_sync_words) {
-  const Geo16 g = geo_of(d);
+  const BlockGeo g = geo_of(d);
   if (g.dt != DT_BF16 && g.dt != DT_F16) return set_error("ms_conv_block_fwd: dtype %d", d->dtype);
   if (d->mode == MS_BN_TRAIN && sg_of(d) > 1 && !stat_pair16_ok(d))
     return set_error("ms_conv_block_fwd: MS_DT_STAT_PAIR is not implemented for this 16-bit block (ms_stat_pair_ok)");
@@ -139,13 +133,12 @@ int block_fwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
   if (!pl.ok) return set_error("ms_conv_block_fwd: no 16-bit kernel for a %dx%d stride (%d,%d) block", d->KH, d->KW, d->SH, d->SW);
   if (d->groups > 1 && ((d->Cout & 7) || (!g.bcast && (d->Cin & 7))))
     return set_error("ms_conv_block_fwd: 16-bit grouped blocks need channels per group %% 8 == 0");
-  if (workspace_bytes < block_fwd16_workspace(d)) return set_error("ms_conv_block_fwd: workspace too small");
+  const Fwd16Layout ws = fwd16_layout(d, pl);
+  if (workspace_bytes < ws.total) return set_error("ms_conv_block_fwd: workspace too small");
   const bool outf32 = out_f32_of(d);
-  char* wsp = (char*)workspace;
-  float* stats = (float*)wsp; wsp += align_up((size_t)pl.n_tiles * g.C * 2 * sizeof(float), 256);
-  float* counts = (float*)wsp; wsp += align_up((size_t)pl.n_tiles * sizeof(float), 256);
-  float* bn_part = nullptr;
-  if (d->mode == MS_BN_TRAIN) { bn_part = (float*)wsp; wsp += bn_part_bytes(d, pl); }
+  float* stats = ws_at<float>(workspace, ws.stats);
+  float* counts = ws_at<float>(workspace, ws.counts);
+  float* bn_part = d->mode == MS_BN_TRAIN ? ws_at<float>(workspace, ws.bn_part) : nullptr;
   // the single-input-channel 3x3 block (AudioEncoder conv.0): vector-unit kernel, no operand preparation
   // (train mode stays on the matrix-pipe kernel: with the tile statistics the vector-unit kernel is the slower one, 46 vs 35 us;
   // eval mode -- the D-step's generator pass -- 41 -> 28.5 us)
@@ -166,7 +159,7 @@ int block_fwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
   if (w_prepared) {
     if (folded) bias_use = (const float*)((const char*)w_prepared + a_bytes) + g.C;
   } else {
-    float* fold = (float*)(wsp + weights16_bytes(d, 0));        // scale | bias'
+    float* fold = ws_at<float>(workspace, ws.fold);        // scale | bias'
     const float* scale = nullptr;
     if (folded) {
       rc = launch_bn_fold(bias, gamma, beta, running_mean, running_var, fold, fold + g.C, g.C, d->eps, s);
@@ -174,10 +167,11 @@ int block_fwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
       scale = fold; bias_use = fold + g.C;
     }
     Prep16Batch pb;
-    pb.n = 1; pb.job[0] = fwd_job(d, pl, w, wsp, scale);
+    void* mine = ws_at<void>(workspace, ws.A);
+    pb.n = 1; pb.job[0] = fwd_job(d, pl, w, mine, scale);
     rc = launch_prep16_multi(pb, s);
     if (rc) return rc;
-    A = wsp;
+    A = mine;
   }
   Conv16Args a = {};
   a.A = A; a.src = x; a.src2 = x2;
@@ -189,18 +183,11 @@ int block_fwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
   a.ep = d->mode == MS_BARE ? EP_BARE : d->mode == MS_BN_TRAIN ? EP_RAW_STATS : (d->mode == MS_LRELU || folded) ? EP_LRELU : EP_BN_EVAL;
   a.bn_g = gamma; a.bn_b = beta; a.bn_m = running_mean; a.bn_v = running_var;
   a.KH = d->KH; a.S = d->SW; a.SV = g.one_d ? 1 : d->SH;
-  if (g.one_d) {
-    a.SRCH = d->B; a.SRCW = d->W; a.s_img = 0; a.s_cblk = d->W; a.s_row = g.cin8_tot * d->W;
-    a.OUTH = d->B; a.OUTW = d->OW; a.o_img = 0; a.o_cblk = d->OW; a.o_row = g.C8 * d->OW;
-    a.of_img = 0; a.of_chan = d->OW; a.of_row = g.C * d->OW;
-    a.PH = 0;
-  } else {
-    a.SRCH = d->H; a.SRCW = d->W; a.s_img = g.cin8_tot * d->H * d->W; a.s_cblk = d->H * d->W; a.s_row = d->W;
-    a.OUTH = d->OH; a.OUTW = d->OW; a.o_img = g.C8 * g.hw; a.o_cblk = g.hw; a.o_row = d->OW;
-    a.of_img = g.C * g.hw; a.of_chan = g.hw; a.of_row = d->OW;
-    a.PH = d->PH;
-  }
-  a.PW = d->PW; a.o_sh = 1; a.o_sw = 1;
+  fill_src8(a, plane_strides(g.one_d, d->B, g.cin8_tot, d->H, d->W));
+  fill_out8(a, plane_strides(g.one_d, d->B, g.C8, d->OH, d->OW));
+  const PlaneStrides of = plane_strides(g.one_d, d->B, g.C, d->OH, d->OW);      // the fp32 output: element strides
+  a.of_img = of.img; a.of_chan = of.chan; a.of_row = of.row;
+  a.PH = g.one_d ? 0 : d->PH; a.PW = d->PW; a.o_sh = 1; a.o_sw = 1;
   a.slope = d->slope; a.eps = d->eps;
   if (outf32 && d->mode != MS_BN_TRAIN) a.out_f32 = (float*)y;
   // train-mode BatchNorm inside the conv launch (conv16_kernel.h, EP_BN_FUSED): the workgroups of a channel tile exchange
@@ -244,18 +231,16 @@ int block_bwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
                 const void* y, const float* save, const void* dy, void* dyr, void* dx, void* dx2, float* dw, float* dbias,
                 float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, hipStream_t s, const void* wt_prepared,
                 float* wgrad_partials, int defer_wgrad_launch) {
-  const Geo16 g = geo_of(d);
+  const BlockGeo g = geo_of(d);
   if (g.dt != DT_BF16 && g.dt != DT_F16) return set_error("ms_conv_block_bwd: dtype %d", d->dtype);
-  if (workspace_bytes < block_bwd16_workspace(d)) return set_error("ms_conv_block_bwd: workspace too small");
+  const Bwd16Layout ws = bwd16_layout(d);
+  if (workspace_bytes < ws.total) return set_error("ms_conv_block_bwd: workspace too small");
   const bool outf32 = out_f32_of(d);
   if (outf32 && d->mode == MS_LRELU) return set_error("ms_conv_block_bwd: fp32 outputs are for BARE and BatchNorm blocks");
-  int bpc;
-  const int nchunk = bwd16_chunks(d->B, g.C8, g.hw, &bpc);
-  char* wsp = (char*)workspace;
-  float* bn_part = (float*)wsp; wsp += align_up((size_t)g.C8 * 8 * nchunk * 2 * sizeof(float), 256);
-  float* colpart = (float*)wsp; wsp += align_up((size_t)g.C8 * 8 * nchunk * sizeof(float), 256);
-  char* wt_ws = wsp; wsp += weights16_bytes(d, 1);
-  float* wg_part = (float*)wsp;
+  float* bn_part = ws_at<float>(workspace, ws.bn_part);
+  float* colpart = ws_at<float>(workspace, ws.colpart);
+  void* wt_ws = ws_at<void>(workspace, ws.wt);
+  float* wg_part = ws_at<float>(workspace, ws.wg_part);
   int rc = 0;
 
   // 1. gradient wrt the raw conv output (+ per-channel column sums = bias gradient)
@@ -276,7 +261,7 @@ int block_bwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
   }
   if (rc) return rc;
   if (dbias && !bias_done) {
-    rc = launch_colsum16(colpart, dbias, g.C, nchunk, s);
+    rc = launch_colsum16(colpart, dbias, g.C, ws.nchunk, s);
     if (rc) return rc;
   }
 
@@ -297,27 +282,9 @@ int block_bwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
     q.Mg = d->Cin; q.groups = dg.tg; q.Kc8g = c8_of(dg.tcog); q.bcast = 0;
     q.ep = g.up2 ? EP_DGRAD_UP2 : EP_BARE; q.is_dgrad = 1;
     q.KH = dg.jh; q.S = 1; q.SV = 1;
-    q.ncls = dg.ncls;
-    double flops = 0;
-    for (int cls = 0; cls < dg.ncls; ++cls) {
-      const int ry = cls / d->SW, rx = cls - ry * d->SW;
-      const int kh0 = (ry + d->PH) % d->SH, kw0 = (rx + d->PW) % d->SW;
-      const int cy = (ry + d->PH - kh0) / d->SH, cx = (rx + d->PW - kw0) / d->SW;
-      const int QH = std::max(0, (d->H - ry + d->SH - 1) / d->SH), QW = std::max(0, (d->W - rx + d->SW - 1) / d->SW);
-      q.cls_PH[cls] = g.one_d ? 0 : (dg.jh - 1) - cy; q.cls_PW[cls] = (dg.jw - 1) - cx;
-      q.cls_OUTH[cls] = g.one_d ? d->B : QH; q.cls_OUTW[cls] = QW;
-      q.cls_ry[cls] = g.one_d ? 0 : ry; q.cls_rx[cls] = rx;
-      flops += 2.0 * d->Cin * dg.tcog * dg.jh * dg.jw * (double)d->B * (g.one_d ? 1 : QH) * QW * dg.tg;
-    }
-    if (g.one_d) {
-      q.SRCH = d->B; q.SRCW = d->OW; q.s_img = 0; q.s_cblk = d->OW; q.s_row = g.C8 * d->OW;
-      q.o_img = 0; q.o_cblk = d->W; q.o_row = g.cin8_tot * d->W; q.o_sh = 1;
-    } else {
-      q.SRCH = d->OH; q.SRCW = d->OW; q.s_img = g.C8 * g.hw; q.s_cblk = g.hw; q.s_row = d->OW;
-      q.o_img = g.cin8_tot * d->H * d->W; q.o_cblk = d->H * d->W; q.o_row = d->W; q.o_sh = d->SH;
-    }
-    q.o_sw = d->SW;
-    q.PH = q.cls_PH[0]; q.PW = q.cls_PW[0]; q.OUTH = q.cls_OUTH[0]; q.OUTW = q.cls_OUTW[0]; q.o_ry = q.cls_ry[0]; q.o_rx = q.cls_rx[0];
+    fill_src8(q, plane_strides(g.one_d, d->B, g.C8, d->OH, d->OW));
+    fill_out8(q, plane_strides(g.one_d, d->B, g.cin8_tot, d->H, d->W));
+    const double flops = fill_parity_classes(q, d, dg, g.one_d);
     q.slope = d->slope; q.eps = d->eps;
     const double bytes = 2.0 * ((double)g.C * d->Cin * d->KH * d->KW + (double)d->B * g.C * g.hw + (double)d->B * g.cin_tot * d->H * d->W);
     rc = launch_conv16(g.dt, q, dg.pl, dg.jw, false, flops, bytes, s);
@@ -328,7 +295,7 @@ int block_bwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
   if (dw) {
     const Wgrad16Plan wp = wgrad_plan16(d);
     if (!wp.tp) return set_error("ms_conv_block_bwd: no 16-bit weight-gradient kernel for this geometry");
-    const size_t wsize = (size_t)g.C * d->Cin * d->KH * d->KW;
+    const size_t wsize = wsize_of(d);
     Wgrad16Args a = {};
     a.dyr = gsrc; a.src = x; a.src2 = x2;
     const bool defer = wgrad_partials != nullptr && wp.splits > 1;
@@ -336,13 +303,9 @@ int block_bwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
     a.out_split_stride = wsize;
     a.Cog = d->Cout; a.Cig = d->Cin; a.groups = d->groups; a.bcast = g.bcast;
     a.KH = d->KH; a.KW = d->KW; a.S = d->SW; a.SV = g.one_d ? 1 : d->SH; a.PW = d->PW;
-    if (g.one_d) {
-      a.SRCH = d->B; a.SRCW = d->W; a.s_img = 0; a.s_cblk = d->W; a.s_row = g.cin8_tot * d->W; a.PH = 0;
-      a.OUTH = d->B; a.OUTW = d->OW; a.o_img = 0; a.o_cblk = d->OW; a.o_row = g.C8 * d->OW;
-    } else {
-      a.SRCH = d->H; a.SRCW = d->W; a.s_img = g.cin8_tot * d->H * d->W; a.s_cblk = d->H * d->W; a.s_row = d->W; a.PH = d->PH;
-      a.OUTH = d->OH; a.OUTW = d->OW; a.o_img = g.C8 * g.hw; a.o_cblk = g.hw; a.o_row = d->OW;
-    }
+    fill_src8(a, plane_strides(g.one_d, d->B, g.cin8_tot, d->H, d->W));
+    fill_out8(a, plane_strides(g.one_d, d->B, g.C8, d->OH, d->OW));
+    a.PH = g.one_d ? 0 : d->PH;
     const double flops = 2.0 * d->Cout * d->Cin * d->KH * d->KW * (double)g.npix * d->groups;
     const double bytes = 2.0 * ((double)g.npix * g.C + (double)d->B * g.cin_tot * d->H * d->W) + 4.0 * (double)wsize;
     // queued form: only when nothing of this call reads the result (dw written in place, or slabs left for the caller)
@@ -406,39 +369,24 @@ int ms_weights16_prepare(int n, const ms_prep16_item* items, void* stream) {
     if (dt_of(d) != DT_BF16 && dt_of(d) != DT_F16) return set_error("ms_weights16_prepare: item %d is not a 16-bit block", i);
     int rc;
     if (it.fwd) {
-      const Conv16Plan pl = plan_conv16((d->H == 1 && d->KH == 1) ? 1 : 2, d->Cout, d->groups, d->Cin, d->KH, d->KW, d->SH, d->SW, d->B,
-                                        d->OH, d->OW, 1, d->in_mode == MS_IN_UP2ADD);
+      const Conv16Plan pl = fwd_plan16(d);
       if (!pl.ok) return set_error("ms_weights16_prepare: item %d: geometry not supported", i);
       const float* scale = nullptr;
       if (bn_folded_of(d)) {
         if (!it.gamma || !it.beta || !it.running_mean || !it.running_var) return set_error("ms_weights16_prepare: item %d: BN tensors missing", i);
         const int C = d->groups * d->Cout;
-        float* fold = (float*)((char*)it.fwd + align_up(conv16_weight_bytes(pl, d->Cout, d->groups, d->Cin, d->KH, d->KW, 1), 256));
+        float* fold = ws_at<float>(it.fwd, align_up(fwd_a_bytes(d, pl), 256));
         rc = launch_bn_fold(it.bias, it.gamma, it.beta, it.running_mean, it.running_var, fold, fold + C, C, d->eps, s);
         if (rc) return rc;
         scale = fold;
       }
-      Prep16Job jb = {};
-      jb.w = it.w; jb.out = it.fwd; jb.scale = scale;
-      jb.groups = d->groups; jb.Cog = d->Cout; jb.Cig = d->Cin; jb.KH = d->KH; jb.KW = d->KW; jb.SH = d->SH; jb.SW = d->SW;
-      jb.PH = d->PH; jb.PW = d->PW; jb.bcast = d->in_mode == MS_IN_BCAST;
-      jb.BM = 64 * pl.wm; jb.CK8 = pl.ck8; jb.nchunks = pl.nchunks; jb.n_mt = cdiv(d->Cout, jb.BM); jb.dt = dt_of(d);
-      pb.job[pb.n++] = jb;
+      pb.job[pb.n++] = fwd_job(d, pl, it.w, it.fwd, scale);
       if (pb.n == PREP16_BATCH_MAX && (rc = flush())) return rc;
     }
     if (it.dgrad) {
-      const bool bc = d->in_mode == MS_IN_BCAST;
-      const int tg = bc ? 1 : d->groups, tcog = bc ? d->groups * d->Cout : d->Cout;
-      const int jh = cdiv(d->KH, d->SH), jw = cdiv(d->KW, d->SW);
-      const Conv16Plan pl = plan_conv16((d->H == 1 && d->KH == 1) ? 1 : 2, d->Cin, tg, tcog, jh, jw, 1, 1, d->B, cdiv(d->H, d->SH),
-                                        cdiv(d->W, d->SW), d->SH * d->SW, false);
-      if (!pl.ok) return set_error("ms_weights16_prepare: item %d: data-gradient geometry not supported", i);
-      Prep16Job jb = {};
-      jb.w = it.w; jb.out = it.dgrad; jb.dgrad = 1;
-      jb.groups = d->groups; jb.Cog = d->Cout; jb.Cig = d->Cin; jb.KH = d->KH; jb.KW = d->KW; jb.SH = d->SH; jb.SW = d->SW;
-      jb.PH = d->PH; jb.PW = d->PW; jb.bcast = bc;
-      jb.BM = 64 * pl.wm; jb.CK8 = pl.ck8; jb.nchunks = pl.nchunks; jb.n_mt = cdiv(d->Cin, jb.BM); jb.dt = dt_of(d);
-      pb.job[pb.n++] = jb;
+      const Dgrad16 dg = dgrad_plan16(d);
+      if (!dg.pl.ok) return set_error("ms_weights16_prepare: item %d: data-gradient geometry not supported", i);
+      pb.job[pb.n++] = dgrad_job(d, dg, it.w, it.dgrad);
       if (pb.n == PREP16_BATCH_MAX && (rc = flush())) return rc;
     }
   }
