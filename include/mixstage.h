@@ -132,6 +132,22 @@ int ms_conv_block_fwd_ex(const ms_conv_desc* d, const float* x, const float* x2,
                          const float* bias, const float* gamma, const float* beta, float* running_mean,
                          float* running_var, float* y_raw, float* y, float* save, void* workspace,
                          size_t workspace_bytes, void* stream, const ms_fwd_options* opt);
+/* Two independent forward blocks in one launch.  ms_clip_hold(stream) arms a one-slot hold: the next ms_conv_block_fwd_ex on that
+ * stream that runs the clip-resident fp32 kernel (ms_clip_grid(d) > 0) is planned but NOT launched (a call that runs other kernels
+ * launches as usual and disarms the hold).  The following ms_conv_block_fwd_ex on the stream takes the held block into its own launch,
+ * on the compute units its grid leaves empty, when the two kernels have a pair instance, its own grid is a multiple of 8 workgroups and
+ * both grids together are at most the device's compute units; otherwise the held block is launched first, then the new one.  Results
+ * are bit for bit those of two launches.  The caller vouches that the two blocks are independent: separate outputs, workspaces and
+ * bn_sync words, nothing else launched on the stream in between needs the held block's results, and every buffer of the held call
+ * stays allocated until the launch that carries it (or the flush) has been issued.  ms_clip_hold_flush launches a
+ * held block now (and disarms); ms_clip_hold_discard drops it (error paths).  ms_clip_hold while a block is pending is an error.
+ * ms_clip_grid: workgroups of d's forward launch on the clip-resident kernel, 0 where d does not run there.
+ * ms_clip_pair_ok: 1 when block `guest`, held, would share block `host`'s launch on the current device. */
+int ms_clip_hold(void* stream);
+int ms_clip_hold_flush(void* stream);
+int ms_clip_hold_discard(void* stream);
+int ms_clip_grid(const ms_conv_desc* d);
+int ms_clip_pair_ok(const ms_conv_desc* host, const ms_conv_desc* guest);
 /* bf16x6 mode (ms_set_precision): bytes of the block's split weight planes (0: the block runs the fp32 kernels), and their
  * batched construction for n blocks in one launch -- once per optimizer update, like ms_dgrad_weights_prepare. */
 size_t ms_fwd_weights_bytes(const ms_conv_desc* d);

@@ -162,6 +162,12 @@ SIGNATURES = {
     'ms_debug_set_conv16_ring': (c_int, [c_int, c_int]),
     'ms_debug_set_skip': (c_int, [ctypes.c_char_p]),
     'ms_debug_set_clip32': (c_int, [c_int]),
+    'ms_debug_set_clip_corun': (c_int, [c_int]),
+    'ms_clip_hold': (c_int, [_P]),
+    'ms_clip_hold_flush': (c_int, [_P]),
+    'ms_clip_hold_discard': (c_int, [_P]),
+    'ms_clip_grid': (c_int, [_DESC]),
+    'ms_clip_pair_ok': (c_int, [_DESC, _DESC]),
     'ms_debug_set_wgrad16_target': (c_int, [c_int]),
     'ms_debug_set_wgrad16_ring': (c_int, [c_int]),
     'ms_debug_set_wgrad_target': (c_int, [c_int]),

@@ -179,10 +179,27 @@ int ms_conv_block_fwd(const ms_conv_desc* d, const float* x, const float* x2, co
                               workspace_bytes, stream, nullptr);
 }
 
+static int conv_block_fwd_impl(const ms_conv_desc* d, const float* x, const float* x2, const float* w, const float* bias,
+                               const float* gamma, const float* beta, float* running_mean, float* running_var, float* y_raw,
+                               float* y, float* save, void* workspace, size_t workspace_bytes, void* stream,
+                               const ms_fwd_options* opt);
+
 int ms_conv_block_fwd_ex(const ms_conv_desc* d, const float* x, const float* x2, const float* w, const float* bias,
                          const float* gamma, const float* beta, float* running_mean, float* running_var, float* y_raw,
                          float* y, float* save, void* workspace, size_t workspace_bytes, void* stream,
                          const ms_fwd_options* opt) {
+  // the stream's hold (ms_clip_hold): a block held back from an earlier call goes first unless this call can share its launch
+  const bool clip_path = d && dt_of(d) == DT_F32 && g_precision == 0 && !validate(d, "ms_conv_block_fwd") && clip32_fwd_ok(d);
+  int rc = clip32_fwd_call_begin((hipStream_t)stream, clip_path, workspace, workspace_bytes);
+  if (!rc) rc = conv_block_fwd_impl(d, x, x2, w, bias, gamma, beta, running_mean, running_var, y_raw, y, save, workspace, workspace_bytes, stream, opt);
+  clip32_fwd_call_end((hipStream_t)stream);
+  return rc;
+}
+
+static int conv_block_fwd_impl(const ms_conv_desc* d, const float* x, const float* x2, const float* w, const float* bias,
+                               const float* gamma, const float* beta, float* running_mean, float* running_var, float* y_raw,
+                               float* y, float* save, void* workspace, size_t workspace_bytes, void* stream,
+                               const ms_fwd_options* opt) {
   const unsigned short* w_planes = opt ? (const unsigned short*)opt->w_planes : nullptr;
   int rc = validate(d, "ms_conv_block_fwd");
   if (rc) return rc;
@@ -216,7 +233,8 @@ int ms_conv_block_fwd_ex(const ms_conv_desc* d, const float* x, const float* x2,
     rc = clip32_block_fwd(d, x, x2, wp, bias, gamma, beta, running_mean, running_var, y_raw, y, save, stats, opt ? opt->bn_sync : nullptr,
                           opt ? opt->bn_sync_words : 0, s);
     if (rc != -2) return rc;          // (-2: BN_TRAIN without counters, or a grid that is not resident at once: the kernels below)
-    rc = 0;
+    rc = clip32_hold_flush(s);        // (... in stream order behind a block the stream's hold may still hold)
+    if (rc) return rc;
   }
 
   float* out = d->mode == MS_BN_TRAIN ? y_raw : y;
@@ -731,6 +749,23 @@ int ms_conv_block_bwd_ex(const ms_conv_desc* d, const float* x, const float* x2,
     rc = launch_wgrad(a, up2, dw, wg_part, defer_wgrad, ws_stream, opt->defer_wgrad_launch && ws_stream == s);
   }
   return rc;
+}
+
+int ms_clip_hold(void* stream) { return clip32_hold_arm((hipStream_t)stream); }
+int ms_clip_hold_flush(void* stream) { return clip32_hold_flush((hipStream_t)stream); }
+int ms_clip_hold_discard(void* stream) { clip32_hold_discard((hipStream_t)stream); return 0; }
+int ms_clip_grid(const ms_conv_desc* d) {
+  if (validate(d, "ms_clip_grid") || dt_of(d) != DT_F32 || g_precision != 0) return 0;
+  return clip32_fwd_grid(d);
+}
+int ms_clip_pair_ok(const ms_conv_desc* host, const ms_conv_desc* guest) {
+  if (validate(host, "ms_clip_pair_ok") || validate(guest, "ms_clip_pair_ok") || dt_of(host) != DT_F32 || dt_of(guest) != DT_F32 || g_precision != 0) return 0;
+  return clip32_fwd_pair_ok(host, guest) ? 1 : 0;
+}
+int ms_debug_set_clip_corun(int on) {
+  const int prev = g_clip_corun < 0 ? 1 : g_clip_corun;
+  g_clip_corun = on ? 1 : 0;
+  return prev;
 }
 
 }  // extern "C"

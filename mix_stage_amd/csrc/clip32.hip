@@ -15,6 +15,8 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <map>
+#include <mutex>
 #include <vector>
 
 #include "kernels.h"
@@ -55,7 +57,7 @@ struct Clip32Args {
                          // x npw / px pixel workgroups, so that what its L2 fetches (weight slices + clip images) is smallest; cx = 0: linear
   unsigned long long* stamps;   // diagnostics (MS_CLIP_DBG=32): [workgroup][8] s_memrealtime stamps (100 MHz)
 };
-#define CL_STAMP(k) do { if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define CL_STAMP(k) do { if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)bid * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 
 __host__ __device__ constexpr int cl_pslots(int n) { return (n + 3) & ~3; }      // slots per plane
 // position of slot s (0 = left halo, 1 + frame, Ti + 1 = right halo) inside a clip's row.  Stride-2 forward: even and odd slots
@@ -95,18 +97,19 @@ __device__ __forceinline__ float cl_sum8(float v) {
 // DG2: data gradient of a k4 s2 p1 block (KW = 4, S = 1, NB = 2): the image holds the Ti = To / 2 frames of dy_raw per clip, output
 // frame 2m is taps (1, 3) at frames (m, m - 1), frame 2m + 1 taps (0, 2) at (m + 1, m): one accumulator per parity, every unit
 // (channel group, tap) feeds the one its tap belongs to -- no zero-stuffed operand, half the matrix work of a k4 s1 conv.
+// The block's body for workgroup `bid` of its grid: the kernel below runs it for a launch of its own, clip32_pair_kernel for one of
+// the two blocks that share a launch.
 template <int KW, int S, int NB, bool UP2, int K8W, bool DG2 = false>
-__global__ __launch_bounds__(256, 1) void clip32_kernel(const Clip32Args p) {
-  prefetch_kernargs<sizeof(Clip32Args)>();
+__device__ __forceinline__ void clip32_body(const Clip32Args& p, const unsigned bid) {
   extern __shared__ float cl_smem[];
   CL_STAMP(0);
   constexpr int NPX = 32 * NB;                       // output frames per workgroup
   constexpr int NWR = (K8W ? K8W : CL_MAXK8W) * KW;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, n0 = lane & 31, h = lane >> 5;
   const int nct = p.nct;
-  int ct = blockIdx.x % nct, pw = blockIdx.x / nct;  // channel tile, pixel workgroup
+  int ct = bid % nct, pw = bid / nct;                // channel tile, pixel workgroup
   if (p.cx) {
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3, tpx = nct / p.cx, ppx = p.npw / p.px;
+    const int xcd = bid & 7, j = bid >> 3, tpx = nct / p.cx, ppx = p.npw / p.px;
     const int xc = xcd % p.cx, xp = xcd / p.cx, jp = j / tpx;
     ct = xc * tpx + (j - jp * tpx);
     pw = xp * ppx + jp;
@@ -633,6 +636,31 @@ __global__ __launch_bounds__(256, 1) void clip32_kernel(const Clip32Args p) {
   CL_STAMP(7);
 }
 
+template <int KW, int S, int NB, bool UP2, int K8W, bool DG2 = false>
+__global__ __launch_bounds__(256, 1) void clip32_kernel(const Clip32Args p) {
+  prefetch_kernargs<sizeof(Clip32Args)>();
+  clip32_body<KW, S, NB, UP2, K8W, DG2>(p, blockIdx.x);
+}
+
+// Two independent forward blocks in ONE launch on disjoint compute units: workgroups [0, nA) are block A's grid, [nA, nA + nB)
+// block B's (with nA % 8 == 0, so that B's workgroups land on the XCDs they would in a launch of their own).  Each block keeps its
+// own partials, meeting counters and sync words; the dynamic LDS is the larger of the two images.
+struct ClipPairArgs {
+  int nA;
+  Clip32Args a, b;
+};
+template <int KWA, int SA, int NBA, bool UP2A, int K8WA, int KWB, int SB, int NBB, bool UP2B, int K8WB>
+__global__ __launch_bounds__(256, 1) void clip32_pair_kernel(const ClipPairArgs pp) {
+  const unsigned bid = blockIdx.x;
+  if (bid < (unsigned)pp.nA) {
+    prefetch_kernargs<sizeof(Clip32Args)>();
+    clip32_body<KWA, SA, NBA, UP2A, K8WA>(pp.a, bid);
+  } else {
+    prefetch_kernargs<384>((int)offsetof(ClipPairArgs, b));
+    clip32_body<KWB, SB, NBB, UP2B, K8WB>(pp.b, bid - (unsigned)pp.nA);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // weights in stream order: [channel tile][wave][k8 local][tap][lane][4] = row 32*ct + (lane & 31), channels
 // 8*(wave*k8w + k8 local) + 4*(lane >> 5) + 0..3.  transposed = 0: w (Cout, Cin, KW), row = output channel;
@@ -800,8 +828,196 @@ static int clip32_launch_t(const Clip32Args& a, int nwg, int lds_bytes, hipStrea
   }
 }
 
+// One planned launch: the arguments as the kernel takes them, the instance, the grid and what the timing label prints.
+struct ClipJob {
+  Clip32Args a;
+  int KW, S, nb, nwg, lds;
+  bool up2, dg2;
+  const char* what;
+  double flops, bytes;
+};
+
+// ---- the pair instances: (host, guest) of the headline path -- a UNet1D block beside a PoseStyleEncoder block.  Anything else is
+// "not mergeable": the two blocks get a launch each.
+enum { CLIP_HOST_DOWN8 = 0, CLIP_HOST_UP8 = 1, CLIP_HOSTS = 2 };                     // <4,2,1,false,8>, <3,1,2,true,8>
+enum { CLIP_GUEST_K3_4 = 0, CLIP_GUEST_DOWN2 = 1, CLIP_GUEST_DOWN4 = 2, CLIP_GUEST_DOWN8 = 3, CLIP_GUESTS = 4 };
+static int clip_host_kind(const ClipJob& j) {
+  if (j.dg2 || j.a.k8w != 8) return -1;
+  if (j.KW == 4 && j.S == 2 && !j.up2) return CLIP_HOST_DOWN8;
+  if (j.KW == 3 && j.S == 1 && j.up2) return CLIP_HOST_UP8;
+  return -1;
+}
+static int clip_guest_kind(const ClipJob& j) {
+  if (j.dg2 || j.up2) return -1;
+  if (j.KW == 3 && j.S == 1) return j.a.k8w == 4 ? CLIP_GUEST_K3_4 : -1;
+  if (j.KW == 4 && j.S == 2) return j.a.k8w == 2 ? CLIP_GUEST_DOWN2 : j.a.k8w == 4 ? CLIP_GUEST_DOWN4 : j.a.k8w == 8 ? CLIP_GUEST_DOWN8 : -1;
+  return -1;
+}
+template <int KWA, int SA, int NBA, bool UP2A, int K8WA, int KWB, int SB, int NBB, bool UP2B, int K8WB>
+static int clip32_pair_launch_k(const ClipPairArgs& pp, int nwg, int lds_bytes, hipStream_t s) {
+  auto fn = clip32_pair_kernel<KWA, SA, NBA, UP2A, K8WA, KWB, SB, NBB, UP2B, K8WB>;
+  static unsigned long long attr_done = 0;          // (per device)
+  if (first_time_on_device(attr_done)) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+      return set_error("clip32: cannot raise the dynamic LDS limit");
+    done_on_device(attr_done);
+  }
+  hipLaunchKernelGGL(fn, dim3(nwg), dim3(256), lds_bytes, s, pp);
+  return check_launch("clip32_pair_kernel");
+}
+template <int KWA, int SA, int NBA, bool UP2A>
+static int clip32_pair_launch_g(int guest, const ClipPairArgs& pp, int nwg, int lds_bytes, hipStream_t s) {
+  switch (guest) {
+    case CLIP_GUEST_K3_4: return clip32_pair_launch_k<KWA, SA, NBA, UP2A, 8, 3, 1, 2, false, 4>(pp, nwg, lds_bytes, s);
+    case CLIP_GUEST_DOWN2: return clip32_pair_launch_k<KWA, SA, NBA, UP2A, 8, 4, 2, 1, false, 2>(pp, nwg, lds_bytes, s);
+    case CLIP_GUEST_DOWN4: return clip32_pair_launch_k<KWA, SA, NBA, UP2A, 8, 4, 2, 1, false, 4>(pp, nwg, lds_bytes, s);
+    default: return clip32_pair_launch_k<KWA, SA, NBA, UP2A, 8, 4, 2, 1, false, 8>(pp, nwg, lds_bytes, s);
+  }
+}
+
+// the launch of one planned block on its own
+static int clip32_issue(ClipJob& j, hipStream_t s) {
+  Clip32Args& a = j.a;
+  const int nwg = j.nwg;
+  TimingScope ts(s, j.flops, j.bytes, "clip32_kernel<%d,%d,%d,%d>|conv_%s_clip k1x%d s%d rows%d red%d T%d B%d ep%d", j.KW, j.S, j.nb, j.up2 ? 1 : 0, j.what,
+                 j.KW, j.S, a.rows_valid, a.Cin, a.To, a.B, a.ep);
+  if (ts.skip()) return 0;
+  static int dbg = -1;
+  if (dbg < 0) { const char* e = getenv("MS_CLIP_DBG"); dbg = e ? atoi(e) : 0; }
+  static unsigned long long* g_stamps = nullptr;
+  if (dbg & 32) {                           // diagnostics only: stamps of every workgroup, printed after a synchronisation
+    if (!g_stamps && hipMalloc(&g_stamps, 4096 * 8 * 8) != hipSuccess) g_stamps = nullptr;
+    if (g_stamps) (void)hipMemsetAsync(g_stamps, 0, 4096 * 8 * 8, s);
+    a.stamps = nwg <= 4096 ? g_stamps : nullptr;
+  }
+  int rc;
+  if (j.dg2) rc = clip32_launch_t<4, 1, 2, false, true>(a, nwg, j.lds, s);
+  else if (j.KW == 3 && j.S == 1) rc = j.up2 ? clip32_launch_t<3, 1, 2, true>(a, nwg, j.lds, s) : clip32_launch_t<3, 1, 2, false>(a, nwg, j.lds, s);
+  else rc = clip32_launch_t<4, 2, 1, false>(a, nwg, j.lds, s);
+  if (a.stamps) {
+    std::vector<unsigned long long> h((size_t)nwg * 8);
+    if (hipStreamSynchronize(s) == hipSuccess && hipMemcpy(h.data(), g_stamps, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+      unsigned long long t0 = ~0ull;
+      for (int i = 0; i < nwg; ++i) t0 = std::min(t0, h[(size_t)i * 8]);
+      fprintf(stderr, "clip32 %s k%d s%d rows%d red%d ep%d: stamps (us after the first workgroup's entry; min / median / max over %d workgroups)\n", j.what, j.KW, j.S,
+              a.rows_valid, a.Cin, a.ep, nwg);
+      for (int k = 0; k < 8; ++k) {
+        std::vector<double> v;
+        for (int i = 0; i < nwg; ++i) if (h[(size_t)i * 8 + k]) v.push_back((double)(h[(size_t)i * 8 + k] - t0) * 0.01);
+        if (v.empty()) continue;
+        std::sort(v.begin(), v.end());
+        fprintf(stderr, "  stamp %d: %7.2f %7.2f %7.2f\n", k, v.front(), v[v.size() / 2], v.back());
+      }
+    }
+    a.stamps = nullptr;
+  }
+  return rc;
+}
+
+// ---- the one-slot hold of a stream (ms_clip_hold): a forward block planned but not yet launched, waiting for the next forward
+// block of the stream to share its launch with.  IDLE -> ARMED (ms_clip_hold) -> PENDING (a clip-path ms_conv_block_fwd_ex recorded
+// its job) -> IDLE (merged, launched alone, or discarded).
+int g_clip_corun = -1;     // ms_debug_set_clip_corun / MS_CLIP_CORUN=0: never merge (A/B runs)
+enum { HOLD_IDLE = 0, HOLD_ARMED = 1, HOLD_PENDING = 2 };
+struct ClipHold {
+  int state = HOLD_IDLE;
+  ClipJob job;
+  const char* ws_lo = nullptr;      // the held call's workspace: a later call that shares it must not run beside it
+  const char* ws_hi = nullptr;
+};
+static std::mutex g_hold_mu;
+static std::map<hipStream_t, ClipHold> g_hold;
+static thread_local bool t_in_fwd = false;            // inside ms_conv_block_fwd_ex (clip32_fwd_call_begin / _end)
+static thread_local const char* t_ws_lo = nullptr;
+static thread_local const char* t_ws_hi = nullptr;
+
+static bool clip_corun_on() {
+  if (g_clip_corun < 0) { const char* e = getenv("MS_CLIP_CORUN"); g_clip_corun = e ? (atoi(e) != 0) : 1; }
+  return g_clip_corun != 0;
+}
+
+int clip32_hold_arm(hipStream_t s) {
+  std::lock_guard<std::mutex> lk(g_hold_mu);
+  ClipHold& h = g_hold[s];
+  if (h.state == HOLD_PENDING) return set_error("ms_clip_hold: a held block is pending on this stream (flush or discard it first)");
+  h.state = HOLD_ARMED;
+  return 0;
+}
+void clip32_hold_discard(hipStream_t s) {
+  std::lock_guard<std::mutex> lk(g_hold_mu);
+  auto it = g_hold.find(s);
+  if (it != g_hold.end()) it->second.state = HOLD_IDLE;
+}
+int clip32_hold_flush(hipStream_t s) {
+  ClipJob job;
+  {
+    std::lock_guard<std::mutex> lk(g_hold_mu);
+    auto it = g_hold.find(s);
+    if (it == g_hold.end()) return 0;
+    const int st = it->second.state;
+    it->second.state = HOLD_IDLE;
+    if (st != HOLD_PENDING) return 0;
+    job = it->second.job;
+  }
+  return clip32_issue(job, s);
+}
+// ms_conv_block_fwd_ex brackets its work with these two.  begin: a pending block whose scratch this call shares, or a call that will
+// not take the clip path, sends the pending block off first (a clip path that declines at run time, -2, does so itself:
+// clip32_hold_flush).  end: a hold that this call did not use is disarmed.
+int clip32_fwd_call_begin(hipStream_t s, bool clip_path, const void* ws, size_t ws_bytes) {
+  t_in_fwd = true;
+  t_ws_lo = (const char*)ws; t_ws_hi = t_ws_lo + (ws ? ws_bytes : 0);
+  bool flush = false;
+  {
+    std::lock_guard<std::mutex> lk(g_hold_mu);
+    auto it = g_hold.find(s);
+    if (it != g_hold.end() && it->second.state == HOLD_PENDING)
+      flush = !clip_path || (t_ws_lo < it->second.ws_hi && it->second.ws_lo < t_ws_hi);
+  }
+  return flush ? clip32_hold_flush(s) : 0;
+}
+void clip32_fwd_call_end(hipStream_t s) {
+  t_in_fwd = false;
+  std::lock_guard<std::mutex> lk(g_hold_mu);
+  auto it = g_hold.find(s);
+  if (it != g_hold.end() && it->second.state == HOLD_ARMED) it->second.state = HOLD_IDLE;      // the call took another path
+}
+
+// host A (the current block) and guest B (the held one) in one launch?  The pair has an instance, A's grid keeps B's XCD placement,
+// the merged grid is resident at once -- the condition under which either block's workgroups may wait for one another --, and the
+// two blocks share neither partials nor counters.
+static bool clip_pair_fits(const ClipJob& A, const ClipJob& B) {
+  if (!clip_corun_on()) return false;
+  if (clip_host_kind(A) < 0 || clip_guest_kind(B) < 0) return false;
+  if (A.nwg % 8) return false;
+  int cus = current_device_cus();
+  if (cus <= 0) cus = 256;
+  return A.nwg + B.nwg <= cus;
+}
+static bool clip_pair_ok(const ClipJob& A, const ClipJob& B) {
+  if (!clip_pair_fits(A, B)) return false;
+  const bool meetA = A.a.ep == EP_RAW_STATS && A.a.npw > 1, meetB = B.a.ep == EP_RAW_STATS && B.a.npw > 1;
+  if (meetA && meetB && (A.a.part == B.a.part || A.a.sync == B.a.sync)) return false;
+  return true;
+}
+static int clip32_issue_pair(ClipJob& A, ClipJob& B, hipStream_t s) {
+  char da[96], db[96];
+  snprintf(da, sizeof(da), "conv_%s_clip k1x%d s%d rows%d red%d T%d B%d ep%d", A.what, A.KW, A.S, A.a.rows_valid, A.a.Cin, A.a.To, A.a.B, A.a.ep);
+  snprintf(db, sizeof(db), "conv_%s_clip k1x%d s%d rows%d red%d T%d B%d ep%d", B.what, B.KW, B.S, B.a.rows_valid, B.a.Cin, B.a.To, B.a.B, B.a.ep);
+  TimingScope ts(s, A.flops + B.flops, A.bytes + B.bytes, "clip32_kernel<%d,%d,%d,%d>+<%d,%d,%d,%d>|%s + %s", A.KW, A.S, A.nb, A.up2 ? 1 : 0, B.KW, B.S,
+                 B.nb, B.up2 ? 1 : 0, da, db);
+  if (ts.skip()) return 0;
+  ClipPairArgs pp;
+  pp.nA = A.nwg; pp.a = A.a; pp.b = B.a;
+  pp.a.stamps = pp.b.stamps = nullptr;
+  const int nwg = A.nwg + B.nwg, lds = std::max(A.lds, B.lds), guest = clip_guest_kind(B);
+  return clip_host_kind(A) == CLIP_HOST_DOWN8 ? clip32_pair_launch_g<4, 2, 1, false>(guest, pp, nwg, lds, s)
+                                              : clip32_pair_launch_g<3, 1, 2, true>(guest, pp, nwg, lds, s);
+}
+
 // ep: EP_BARE / EP_LRELU / EP_BN_EVAL / EP_RAW_STATS (= BN_TRAIN, everything in this launch) / EP_DGRAD_UP2
-int clip32_launch(Clip32Args a, int KW, int S, bool up2, const char* what, hipStream_t s, bool dg2 = false) {
+// plan_only: fills *plan and launches nothing (ms_clip_grid)
+int clip32_launch(Clip32Args a, int KW, int S, bool up2, const char* what, hipStream_t s, bool dg2 = false, ClipJob* plan = nullptr) {
   const int nb = (S == 2 && !dg2) ? 1 : 2, npx = 32 * nb;
   a.k8w = clip_k8w(a.Cin);
   a.npw = a.B * a.To / npx;
@@ -837,40 +1053,57 @@ int clip32_launch(Clip32Args a, int KW, int S, bool up2, const char* what, hipSt
   // (one workgroup per CU is what every instance of the kernel is sure to get: LDS would allow two of the smaller images, the
   // register file of the upsample-add instance does not)
   if ((a.ep == EP_RAW_STATS || a.ep == EP_DGRAD_BN) && a.npw > 1 && nwg > cus) return -2;      // caller falls back to the per-layer kernels
-  const double flops = 2.0 * a.rows_valid * a.Cin * (dg2 ? 2 : KW) * (double)a.B * a.To;
-  const double bytes = 4.0 * ((double)a.rows_valid * a.Cin * KW + (double)a.B * a.Cin * a.Ti + (double)a.B * a.rows_valid * a.To);
-  TimingScope ts(s, flops, bytes, "clip32_kernel<%d,%d,%d,%d>|conv_%s_clip k1x%d s%d rows%d red%d T%d B%d ep%d", KW, S, nb, up2 ? 1 : 0, what, KW,
-                 S, a.rows_valid, a.Cin, a.To, a.B, a.ep);
-  if (ts.skip()) return 0;
-  static int dbg = -1;
-  if (dbg < 0) { const char* e = getenv("MS_CLIP_DBG"); dbg = e ? atoi(e) : 0; }
-  static unsigned long long* g_stamps = nullptr;
-  if (dbg & 32) {                           // diagnostics only: stamps of every workgroup, printed after a synchronisation
-    if (!g_stamps && hipMalloc(&g_stamps, 4096 * 8 * 8) != hipSuccess) g_stamps = nullptr;
-    if (g_stamps) (void)hipMemsetAsync(g_stamps, 0, 4096 * 8 * 8, s);
-    a.stamps = nwg <= 4096 ? g_stamps : nullptr;
-  }
-  int rc;
-  if (dg2) rc = clip32_launch_t<4, 1, 2, false, true>(a, nwg, lds, s);
-  else if (KW == 3 && S == 1) rc = up2 ? clip32_launch_t<3, 1, 2, true>(a, nwg, lds, s) : clip32_launch_t<3, 1, 2, false>(a, nwg, lds, s);
-  else rc = clip32_launch_t<4, 2, 1, false>(a, nwg, lds, s);
-  if (a.stamps) {
-    std::vector<unsigned long long> h((size_t)nwg * 8);
-    if (hipStreamSynchronize(s) == hipSuccess && hipMemcpy(h.data(), g_stamps, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-      unsigned long long t0 = ~0ull;
-      for (int i = 0; i < nwg; ++i) t0 = std::min(t0, h[(size_t)i * 8]);
-      fprintf(stderr, "clip32 %s k%d s%d rows%d red%d ep%d: stamps (us after the first workgroup's entry; min / median / max over %d workgroups)\n", what, KW, S,
-              a.rows_valid, a.Cin, a.ep, nwg);
-      for (int k = 0; k < 8; ++k) {
-        std::vector<double> v;
-        for (int i = 0; i < nwg; ++i) if (h[(size_t)i * 8 + k]) v.push_back((double)(h[(size_t)i * 8 + k] - t0) * 0.01);
-        if (v.empty()) continue;
-        std::sort(v.begin(), v.end());
-        fprintf(stderr, "  stamp %d: %7.2f %7.2f %7.2f\n", k, v.front(), v[v.size() / 2], v.back());
+  ClipJob job;
+  job.a = a; job.KW = KW; job.S = S; job.nb = nb; job.nwg = nwg; job.lds = lds; job.up2 = up2; job.dg2 = dg2; job.what = what;
+  job.flops = 2.0 * a.rows_valid * a.Cin * (dg2 ? 2 : KW) * (double)a.B * a.To;
+  job.bytes = 4.0 * ((double)a.rows_valid * a.Cin * KW + (double)a.B * a.Cin * a.Ti + (double)a.B * a.rows_valid * a.To);
+  if (plan) { *plan = job; return 0; }
+  if (t_in_fwd) {
+    // a forward block inside ms_conv_block_fwd_ex: the stream's hold takes it (ARMED), or hands over the block it holds (PENDING)
+    ClipJob held;
+    int st;
+    {
+      std::lock_guard<std::mutex> lk(g_hold_mu);
+      auto it = g_hold.find(s);
+      st = it == g_hold.end() ? HOLD_IDLE : it->second.state;
+      if (st == HOLD_ARMED) {
+        it->second.state = HOLD_PENDING;
+        it->second.job = job;
+        it->second.ws_lo = t_ws_lo; it->second.ws_hi = t_ws_hi;
+      } else if (st == HOLD_PENDING) {
+        it->second.state = HOLD_IDLE;
+        held = it->second.job;
       }
     }
+    if (st == HOLD_ARMED) return 0;
+    if (st == HOLD_PENDING) {
+      if (clip_pair_ok(job, held)) return clip32_issue_pair(job, held, s);
+      const int rc = clip32_issue(held, s);
+      if (rc) return rc;
+    }
   }
-  return rc;
+  return clip32_issue(job, s);
+}
+
+// the workgroups of block d's forward launch on the clip path, 0 where it does not run there (as clip32_block_fwd decides, given counters)
+static int clip32_fwd_plan(const ms_conv_desc* d, ClipJob* plan) {
+  if (!clip32_fwd_ok(d)) return 0;
+  Clip32Args a = {};
+  a.B = d->B; a.Cin = d->Cin; a.Cout = d->Cout; a.rows_valid = d->Cout; a.To = d->OW; a.Ti = d->W;
+  a.ep = d->mode == MS_BARE ? EP_BARE : d->mode == MS_LRELU ? EP_LRELU : d->mode == MS_BN_EVAL ? EP_BN_EVAL : EP_RAW_STATS;
+  a.sg = a.ep == EP_RAW_STATS ? sg_of(d) : 1;
+  plan->nwg = 0;
+  if (clip32_launch(a, d->KW, d->SW, d->in_mode == MS_IN_UP2ADD, "fwd", nullptr, false, plan) != 0) return 0;
+  return plan->nwg;
+}
+int clip32_fwd_grid(const ms_conv_desc* d) {
+  ClipJob plan;
+  return clip32_fwd_plan(d, &plan);
+}
+// would block `guest`, held, share block `host`'s launch (given separate scratch and counters)?
+bool clip32_fwd_pair_ok(const ms_conv_desc* host, const ms_conv_desc* guest) {
+  ClipJob A, B;
+  return clip32_fwd_plan(host, &A) > 0 && clip32_fwd_plan(guest, &B) > 0 && clip_pair_fits(A, B);
 }
 
 int clip32_block_fwd(const ms_conv_desc* d, const float* x, const float* x2, const float* wp, const float* bias, const float* gamma,

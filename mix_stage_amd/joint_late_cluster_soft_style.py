@@ -128,16 +128,22 @@ class JointLateClusterSoftStyle4_G(nn.Module):
     dt = getattr(self, '_ms_dt', 0)       # 16-bit modes: cb8 tensors between the conv blocks, fp32 at the boundaries
     if dt:
       x = ops16.to_cb8(x, dt)
-    x = self.unet(x)                                            # (B, 256, T) channel-major throughout
+    style = kwargs['style']
+    pose_style_encoder_flag = not kwargs['sample_flag'] and (kwargs['description'] == 'train' or not self.train_only)
+    pose_style_score = None
+    if pose_style_encoder_flag and not dt and isinstance(y, torch.Tensor):
+      # the style encoder reads only y, the UNet only x: its blocks ride in the UNet's half-empty launches (PoseStyleEncoder.forward_beside)
+      x, pose_style_score = self.pose_style_encoder.forward_beside(y, self.unet, x)
+    else:
+      x = self.unet(x)                                          # (B, 256, T) channel-major throughout
     x = ops.backward_marker(x)       # (data-parallel trainers: the decoder / classifier gradients are complete here)
     B, T = x.shape[0], x.shape[2]
 
     ## Pose Style
-    style = kwargs['style']
-    pose_style_encoder_flag = not kwargs['sample_flag'] and (kwargs['description'] == 'train' or not self.train_only)
     if pose_style_encoder_flag:
       mode = 'lin'
-      pose_style_score = self.pose_style_encoder(y)             # (B, S)
+      if pose_style_score is None:
+        pose_style_score = self.pose_style_encoder(y)           # (B, S)
       style_id = style[:, 0].contiguous()                       # one copy of the strided column for both cross-entropy terms
       id_in_loss = ops.cross_entropy(pose_style_score, style_id, scale=self.lambda_id)
       if self.softmax:

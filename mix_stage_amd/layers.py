@@ -195,6 +195,18 @@ class ConvNormRelu(nn.Module):
                           n.running_mean, n.running_var, x2=x2, in_mode=in_mode, chain_prev=chain_prev and mode == MS_BN_TRAIN,
                           link=link)
 
+  def _next_desc(self, x):
+    """The descriptor the fp32 block would run on the plain input x (ops.corun plans with it), None where that is not one launch."""
+    n = self.norm
+    if self._nd != 1 or getattr(self, '_ms_dt', 0) or x.dim() != 3 or (self._p and self.training):
+      return None
+    train = self.training and n.track_running_stats
+    if train and ops.bn_sync_active():
+      return None
+    w = self.conv.weight
+    return self._geometry().desc(x.shape[0], w.shape[1], 1, x.shape[2], w.shape[0] // self.conv.groups, MS_BN_TRAIN if train else MS_BN_EVAL,
+                                 MS_IN_PLAIN, 0)
+
   def forward(self, x, **kwargs):
     # `_residual` / `_broadcast` / `_out_f32` select the fused forms below (package-internal; the reference's
     # forward(x, **kwargs) ignores its kwargs)
@@ -345,6 +357,16 @@ class _TimeMajorStack(nn.Module):
     return x
 
 
+def _chain_steps(stack, x):
+  """The fp32 form of _TimeMajorStack._chain as a generator, one block per resume (ops.corun): yields the descriptor of the block
+  the next resume runs, returns the chain's result."""
+  x = ops.to_channel_major(x)
+  for i, m in enumerate(stack.conv):
+    yield m._next_desc(x)
+    x = m(x, _ms_chain=_chain_ok(stack.conv, i))
+  return x
+
+
 def _same_res_specs(cin):
   return ((cin, 64, False), (64, 64, False), (64, 128, False), (128, 128, False), (128, 256, False),
           (256, 256, False))
@@ -391,9 +413,25 @@ class PoseStyleEncoder(_TimeMajorStack):
                  (256, 256, True), (256, num_speakers, True)), kernel_size, stride, p, groups)
 
   def forward(self, x, time_steps=None):
-    x = self._chain(x, last_f32=True)
+    return self._score(self._chain(x, last_f32=True))
+
+  @staticmethod
+  def _score(x):
     x = x.mean(-1) if x.shape[-1] > 1 else x.squeeze(-1)   # mean over a length-1 axis is the identity
     return x.squeeze(dim=-1)
+
+  def forward_beside(self, x, host, host_x):
+    """-> (host(host_x), self(x)): this encoder's blocks share the launches of `host`'s blocks (a UNet1D) where those leave compute
+    units empty (ops.corun).  The two modules share no state, so every result is bit for bit what one after the other gives; it
+    stands aside -- exactly that order -- for the 16-bit and bf16x6 modes, bn_sync='global', CPU or float64 tensors, and whenever
+    a block of either module is hooked."""
+    blocks = [m for m in list(host.modules()) + list(self.modules()) if isinstance(m, ConvNormRelu)]
+    if (getattr(self, '_ms_dt', 0) or getattr(host, '_ms_dt', 0) or ops16.is_cb8(host_x) or not ops.corun_ok(x, host_x)
+        or any(p.dtype != torch.float32 for p in self.parameters()) or _hooked(host, self, *blocks)):
+      out = host(host_x)
+      return out, self(x)
+    out, z = ops.corun(lambda: host(host_x), _chain_steps(self, x), x.device)
+    return out, self._score(z)
 
 
 class ClusterClassify(nn.Module):

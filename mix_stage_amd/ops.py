@@ -55,10 +55,15 @@ def _ensure_counters(device):
 
 
 
+_corun = {'driver': None, 'held': False, 'keep': [], 'on': os.environ.get('MS_CLIP_CORUN', '1') != '0', 'merges_offered': 0}
+
+
 def workspace(nbytes, device):
   """Scratch of the CURRENT stream on `device`, grown geometrically.  Users on one stream are serialised by it; two streams
   that run blocks concurrently get a buffer each (partial tiles, BatchNorm partials and split reductions live here)."""
   key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream)
+  if _corun['held']:
+    key = key + ('held',)                  # a block that will share the next block's launch (corun) cannot share its scratch
   if USE_IN_LAUNCH_SPLIT_REDUCTION:
     _ensure_counters(device)
   ws = _workspaces.get(key)
@@ -457,6 +462,10 @@ class _ConvBlockFn(torch.autograd.Function):
       check(lib().ms_conv_block_fwd_ex(ctypes.byref(d), _ptr(x), _ptr(x2), _ptr(w), _ptr(bias), _ptr(gamma), _ptr(beta),
                                        _ptr(rm), _ptr(rv), _ptr(y_raw), _ptr(y), _ptr(save), _ptr(ws), ws.numel(),
                                        _stream(), ctypes.byref(opt)), 'ms_conv_block_fwd_ex')
+      if _corun['held']:
+        # planned, not launched yet (ms_clip_hold): everything the launch touches stays allocated until it is on the stream --
+        # without autograd nothing else holds y_raw / save / the input, and the allocator would hand them to the next taker
+        _corun['keep'].append((x, x2, w, bias, gamma, beta, rm, rv, y_raw, y, save, ws, planes, sync))
     ctx.geom_desc = d
     ctx.mode, ctx.in_mode = mode, in_mode
     # `prev`: the autograd node of the BN_TRAIN block that produced x, handed over by a container that knows x has no other
@@ -659,8 +668,110 @@ def conv_block(x, w, bias, geom, mode, gamma=None, beta=None, running_mean=None,
   stats = (running_mean, running_var) if running_mean is not None else None
   # chain_prev: the caller vouches that x -- the output of another conv block -- feeds nothing but this block
   prev = x.grad_fn if (chain_prev and _chain_fusion['on'] and x.grad_fn is not None and type(x.grad_fn).__name__ == '_ConvBlockFnBackward') else None
-  return _ConvBlockFn.apply(x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, None, prev,
-                            link if (link is not None and _chain_fusion['on'] and torch.is_grad_enabled()) else None)
+  link = link if (link is not None and _chain_fusion['on'] and torch.is_grad_enabled()) else None
+  # a guest chain rides along (corun): its next block is planned now and shares this block's launch, or nothing happens
+  drv = _corun['driver']
+  held = drv is not None and not drv.in_guest and geom.nd == 1 and drv.offer(x, x2, w, geom, mode, in_mode)
+  if not held:
+    return _ConvBlockFn.apply(x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, None, prev, link)
+  try:
+    y = _ConvBlockFn.apply(x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, None, prev, link)
+    check(lib().ms_clip_hold_flush(_stream()), 'ms_clip_hold_flush')      # (a block this launch did not take goes now)
+  except BaseException:
+    lib().ms_clip_hold_discard(_stream())
+    raise
+  finally:
+    _corun['keep'].clear()               # (launched, in stream order from here on -- or dropped)
+  return y
+
+
+# ------------------------------------------------------------------------------------------------
+# Two independent 1-D stacks in the same launches.  A block of the clip-resident fp32 kernel fills at most its channel tiles x pixel
+# workgroups of the device's compute units; where a HOST block leaves room, the next block of an independent GUEST chain is planned
+# first (ms_clip_hold), and the host's launch carries both on disjoint compute units (csrc/clip32.hip: clip32_pair_kernel) -- the
+# guest's launch drops off the step's chain of dependent launches.  Same kernels' bodies on the same arguments: the same bits.
+class _CoRun:
+  """Drives `guest_steps` -- a generator that yields the descriptor of the block its next resume runs (None: not a candidate) and
+  returns the chain's result -- beside the conv blocks that run while it is ops._corun['driver']."""
+
+  def __init__(self, guest_steps, device):
+    self.gen, self.in_guest, self.done, self.result = guest_steps, False, False, None
+    self.cus = torch.cuda.get_device_properties(device).multi_processor_count
+    self.next_desc = None
+    self._resume()           # up to the first block (the chain's own preparation runs here)
+
+  def _resume(self):
+    self.in_guest = True
+    try:
+      self.next_desc = next(self.gen)
+    except StopIteration as e:
+      self.done, self.result, self.next_desc = True, e.value, None
+    finally:
+      self.in_guest = False
+
+  def offer(self, x, x2, w, geom, mode, in_mode):
+    """Called in front of a host block: True when the guest's next block is now held for this block's launch."""
+    if self.done or self.next_desc is None or not x.is_cuda or x.dtype != torch.float32 or w.dtype != torch.float32:
+      return False
+    ref = x2 if in_mode == MS_IN_UP2ADD else x
+    if ref is None or ref.dim() != 3:
+      return False
+    L = lib()
+    d = geom.desc(x.shape[0], w.shape[1], 1, ref.shape[2], w.shape[0] // geom.groups, mode, in_mode, 0)
+    # (both on the clip path, a pair instance of the two kernels, the host's grid a multiple of 8, both grids within the device)
+    n_host, n_guest = L.ms_clip_grid(ctypes.byref(d)), L.ms_clip_grid(ctypes.byref(self.next_desc))
+    if not n_host or not n_guest or n_host + n_guest > self.cus or not L.ms_clip_pair_ok(ctypes.byref(d), ctypes.byref(self.next_desc)):
+      return False
+    stream = _stream()
+    check(L.ms_clip_hold(stream), 'ms_clip_hold')
+    _corun['held'] = True
+    try:
+      self._resume()
+    except BaseException:
+      L.ms_clip_hold_discard(stream)
+      raise
+    finally:
+      _corun['held'] = False
+    _corun['merges_offered'] += 1
+    return True
+
+  def finish(self):
+    """The rest of the guest chain, block by block as it would run alone."""
+    while not self.done:
+      self._resume()
+    return self.result
+
+
+def corun(host_fn, guest_steps, device):
+  """host_fn() with the chain `guest_steps` riding along -> (host_fn's result, the chain's result)."""
+  if _corun['driver'] is not None:
+    raise RuntimeError('corun: a guest chain is already riding along')
+  try:
+    drv = _CoRun(guest_steps, device)
+    _corun['driver'] = drv
+    try:
+      out = host_fn()
+    finally:
+      _corun['driver'] = None
+    return out, drv.finish()
+  except BaseException:
+    _corun['driver'] = None
+    lib().ms_clip_hold_discard(_stream())
+    _corun['keep'].clear()
+    raise
+
+
+def corun_ok(*tensors):
+  """The co-run applies to the fp32 arithmetic on the exact-fp32 kernels, with every BatchNorm meeting inside its block's launch."""
+  from . import ops16
+  return bool(_corun['on'] and _corun['driver'] is None and not bn_sync_active() and not _stat_pair['on'] and ops16.in_launch_meetings()
+              and lib().ms_get_precision() == 0 and all(t.is_cuda and t.dtype == torch.float32 for t in tensors))
+
+
+def enable_corun(on):
+  old = _corun['on']
+  _corun['on'] = bool(on)
+  return old
 
 
 # ------------------------------------------------------------------------------------------------
