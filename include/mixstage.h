@@ -91,7 +91,22 @@ int ms_abi_version(void);
  * passes one after the other. */
 int ms_stat_pair_ok(const ms_conv_desc* d);
 
-/* Bytes of scratch the forward / backward of this block needs. */
+/* Bytes of scratch the forward / backward of this block needs.
+ * The workspace contract -- for these two, ms_decoder_chain_workspace, ms_decoder_chain_eval_workspace, ms_bn_bwd_workspace and
+ * the `partials` / seg_scratch arguments of the loss and optimizer entry points (ms_reduce_partials_count):
+ *   - the contents are unspecified on entry and on return: a call writes what it reads, whatever the buffer held (NaN bit patterns
+ *     included), and leaves nothing there that a later call relies on -- nothing is carried between calls through a workspace;
+ *   - the bytes the size function names are the only ones touched: a buffer of exactly that size, with live tensors right behind
+ *     it, is enough, and a call handed fewer bytes (workspace_bytes) returns an error before it launches or writes anything;
+ *   - the base is aligned to 16 bytes, as for tensors;
+ *   - the size follows the kernel choice: ask again after ms_set_precision or a tuning knob moved (ms_tuning_epoch).
+ * The caller-owned buffers that exist to carry data to a later call -- the prepared operands (ms_dgrad_weights_elems,
+ * ms_fwd_weights_bytes, ms_weights16_bytes, ms_decoder_chain_prepared_bytes) and the weight-gradient slabs that
+ * ms_wgrad_reduce_multi reads (ms_wgrad_partials_elems) -- share the first half only: unspecified on entry (the prepare call or
+ * the backward writes every byte a later call reads), only the named bytes touched, 16-byte aligned, sized per kernel choice.
+ * Their contents after the producing call are, of course, what the consuming call is handed.
+ * Zero-initialised state is no scratch and is named as such where it appears (bn_sync / sync words, the counter buffer).
+ * tests/test_gpu_scratch_contract.py runs every such entry point on exactly-sized, poisoned buffers between guard regions. */
 size_t ms_conv_block_fwd_workspace(const ms_conv_desc* d);
 size_t ms_conv_block_bwd_workspace(const ms_conv_desc* d);
 
@@ -181,8 +196,13 @@ typedef struct ms_bwd_options {
                                  * every queued block in a few multi-block launches (the small layers' weight gradients
                                  * are latency-bound one-wave kernels: side by side they cost one such latency).  x, x2,
                                  * dy / dyr and dw / wgrad_partials must stay valid until the flush; a queued kernel that
-                                 * writes dw itself ADDS to it (dw holds zeros or the step's other contributions).  Blocks
-                                 * whose kernel cannot be queued (bf16x6, im2col-gather path) launch at once as before. */
+                                 * writes dw itself ADDS to it, so dw must hold zeros or the step's other contributions.
+                                 * The im2col-gather path is queued like the patch-staged kernels (same accumulation into
+                                 * dw, same lifetime rule): ms_wgrad_flush is required after any backward call that set this
+                                 * flag.  Launched at once, overwriting dw, are only: bf16x6 blocks (their kernel cannot be
+                                 * queued), the single-input-channel weight gradient (fp32 and 16-bit), a weight gradient that
+                                 * runs on another stream (side_stream), and a block whose dw needs a pixel split while no
+                                 * wgrad_partials were handed over (its reduction cannot wait). */
   /* --- fusing the BatchNorm + LeakyReLU backward of the block that PRODUCED this block's input into this block's data-gradient
    * launch (layers.py:77-78 under loss.backward(), trainer.py:1139; fp32 1-D blocks that ms_dgrad_fuses_prev_bn() accepts).
    * prev_*: the producer's output y, y_raw, save vector, gamma and gradient slots (prev_dgamma / prev_dbeta / prev_dbias may be

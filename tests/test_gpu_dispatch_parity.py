@@ -93,8 +93,18 @@ def _ref_device(e):
   return DEV if (e['nd'] == 2 or macs > 5e8) else 'cpu'
 
 
-def _run_fp32(e, labels):
-  """fp32 / bf16x6 block: device output and gradients under timing, fp64 reference with the device's LeakyReLU mask."""
+def _block_saved(y):
+  """The `save` vector the conv block's autograd node keeps for its backward pass (readable until that pass has run).  (y_raw is
+  no result to compare: the in-launch BatchNorm forms write it only for the channels whose map does not invert from y.)"""
+  fn = y.grad_fn
+  if fn is None or type(fn).__name__ not in ('_ConvBlockFnBackward', '_ConvBlock16FnBackward'):
+    return None
+  return fn.saved_tensors[6]
+
+
+def _run_fp32(e, labels, keep=None):
+  """fp32 / bf16x6 block: device output and gradients under timing, fp64 reference with the device's LeakyReLU mask.
+  keep: a dict that receives the device tensors of the run (output, every gradient, running statistics, save)."""
   import mix_stage_amd as A
   from mix_stage_amd import ops
   from mix_stage_amd.layers import bare_conv
@@ -139,8 +149,18 @@ def _run_fp32(e, labels):
       else:
         y = hip(xh[0])
     gy = torch.randn(y.shape, generator=gen)
+    if keep is not None:
+      keep['y'] = y.detach()
+      keep['save'] = _block_saved(y)
     if mode != 'BN_EVAL':
       y.backward(gy.to(DEV))
+  if keep is not None:
+    for i, x in enumerate(xh):
+      keep['dx%d' % i] = x.grad
+    keep['dw'], keep['dbias'] = hip_conv.weight.grad, hip_conv.bias.grad
+    if bn:
+      keep['dgamma'], keep['dbeta'] = hip.norm.weight.grad, hip.norm.bias.grad
+      keep['running_mean'], keep['running_var'] = hip.norm.running_mean.detach(), hip.norm.running_var.detach()
 
   # ---- fp64 reference: conv (+ BatchNorm, per half for the paired pass) in float64, then the activation with the device's mask
   x64 = [x.double().to(rdev).requires_grad_() for x in xs]
@@ -190,7 +210,7 @@ def _run_fp32(e, labels):
   return errs
 
 
-def _run_16(e, labels):
+def _run_16(e, labels, keep=None):
   """16-bit block: test_gpu_kernels16._case (fp64 on the rounded operands, its bars) under timing.  The LeakyReLU slopes of the
   reference follow the device output's sign (_case mask='device': only elements within one 16-bit rounding of 0 may differ, and
   few of them); eval blocks have no backward pass and compare exact math."""
@@ -203,15 +223,15 @@ def _run_16(e, labels):
     measured = _case(nd, e['B'], e['cin'], e['cout'], e['groups'], e['k'], e['s'], e['p'], H, W, MODES[e['mode']],
                      IN_MODES[e['in_mode']], e['out_f32'], dt=dt, seed=zlib.crc32(e['id'].encode()) % 1000,
                      mask='device' if e['mode'] in ('BN_TRAIN', 'LRELU') else 'exact', ref_dev=_ref_device(e),
-                     bn_folded=e['folded'])
+                     bn_folded=e['folded'], keep=keep)
   return measured
 
 
-def run_entry(e):
-  """-> (labels, {check: (measured, bar)}) for one table entry."""
+def run_entry(e, keep=None):
+  """-> (labels, {check: (measured, bar)}) for one table entry; keep: a dict that receives the run's device tensors."""
   labels = []
   with _knobs(e):
-    errs = (_run_16 if e['prec'] in ('bf16', 'fp16') else _run_fp32)(e, labels)
+    errs = (_run_16 if e['prec'] in ('bf16', 'fp16') else _run_fp32)(e, labels, keep)
   return labels, errs
 
 

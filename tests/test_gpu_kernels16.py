@@ -18,7 +18,7 @@ def _round(t, dt):
 
 
 def _case(nd, B, cin, cout, groups, k, s, p, H, W, mode, in_mode=PLAIN, out_f32=False, dt=torch.bfloat16, seed=0, fragile=False,
-          slope=0.2, grad_tol=None, mask='exact', ref_dev='cpu', bn_folded=False, flip_frac=2e-3):
+          slope=0.2, grad_tol=None, mask='exact', ref_dev='cpu', bn_folded=False, flip_frac=2e-3, keep=None):
   """One 16-bit block against fp64 on its rounded operands.  Returns {check: (measured, bar)}, values relative to the
   reference's max-abs.
 
@@ -26,7 +26,8 @@ def _case(nd, B, cin, cout, groups, k, s, p, H, W, mode, in_mode=PLAIN, out_f32=
   launch of its own it normalises the STORED 16-bit conv output, so a pre-activation within one 16-bit rounding of 0 may take
   the other slope than in exact math; such elements (at most `flip_frac` of the output, each within one rounding of the conv
   output -- carried through BatchNorm's affine map -- of 0) follow the device, and every bar stays as it is.
-  ref_dev: where the float64 reference runs.  bn_folded: eval BatchNorm folded into the weights (the inference form)."""
+  ref_dev: where the float64 reference runs.  bn_folded: eval BatchNorm folded into the weights (the inference form).
+  keep: a dict that receives the device tensors of the run (output, every gradient, running statistics, save)."""
   from mix_stage_amd import ops, ops16
   from mix_stage_amd._lib import MS_BF16, MS_F16
   msdt = MS_BF16 if dt == torch.bfloat16 else MS_F16
@@ -71,8 +72,14 @@ def _case(nd, B, cin, cout, groups, k, s, p, H, W, mode, in_mode=PLAIN, out_f32=
   ctot = cout * groups
   y32 = y if out_f32 else ops16.from_cb8(y, ctot)
   dyv = torch.randn(y32.shape, generator=g).to(DEV)
+  if keep is not None:
+    fn = y.grad_fn
+    keep.update(y=y.detach(), save=fn.saved_tensors[6] if (fn is not None and type(fn).__name__ == '_ConvBlock16FnBackward') else None)
   if mode != BN_EVAL:
     (y32 * dyv).sum().backward()
+  if keep is not None:
+    keep.update(dw=wp.grad, dbias=bp.grad, dgamma=gp.grad, dbeta=bep.grad, running_mean=rm_h, running_var=rv_h)
+    keep.update(dx0=a.grad, dx1=r.grad) if in_mode == UP2 else keep.update(dx0=x.grad)
 
   # ---- fp64 reference on the rounded operands
   rdev = ref_dev
