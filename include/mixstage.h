@@ -225,9 +225,14 @@ typedef struct ms_bwd_options {
                                  * output twice, layers.py:139-151: as the next block's input and as the up path's residual), so
                                  * that dx leaves as the complete gradient of x and no separate accumulation launch runs.  Only for
                                  * blocks ms_dgrad_takes_accum() accepts; composes with prev_*: the sum is what the producer's
-                                 * BatchNorm backward sees. */
+                                 * BatchNorm backward sees.  In the 16-bit modes the pointer is a cb8 tensor of the block's dtype
+                                 * (dx's own type, shape and zero pad channels): it joins the fp32 accumulators, so dx is rounded
+                                 * to 16 bits once.  On a block that declines, or with dx == NULL, the call is an error, launches
+                                 * nothing and writes nothing. */
 } ms_bwd_options;
-/* 1 when block d's data-gradient launch can add ms_bwd_options.dx_accum itself (fp32 clip-resident 1-D blocks, plain input). */
+/* 1 when block d's data-gradient launch can add ms_bwd_options.dx_accum itself: fp32 clip-resident 1-D blocks with a plain input; in
+ * the 16-bit modes every plain-input block whose data gradient has a kernel (1-D and 2-D, stride 1 and 2, grouped -- dx is a cb8
+ * tensor whatever MS_DT_OUT_F32 says about y).  Upsample-add and broadcast inputs are declined. */
 int ms_dgrad_takes_accum(const ms_conv_desc* d);
 /* 1 when block d's data-gradient launch can carry the BatchNorm backward of the producer of its input (see ms_bwd_options.prev_*). */
 int ms_dgrad_fuses_prev_bn(const ms_conv_desc* d);

@@ -476,7 +476,8 @@ int ms_dgrad_fuses_prev_bn(const ms_conv_desc* d) {
 
 int ms_dgrad_takes_accum(const ms_conv_desc* d) {
   if (!d || validate(d, "ms_dgrad_takes_accum")) return 0;
-  return (dt_of(d) == DT_F32 && g_precision == 0 && d->in_mode == MS_IN_PLAIN && clip32_dgrad_ok(d)) ? 1 : 0;
+  if (dt_of(d) != DT_F32) return dgrad16_takes_accum(d) ? 1 : 0;
+  return (g_precision == 0 && d->in_mode == MS_IN_PLAIN && clip32_dgrad_ok(d)) ? 1 : 0;
 }
 
 int ms_conv_block_bwd(const ms_conv_desc* d, const float* x, const float* x2, const float* w, const float* gamma,
@@ -530,7 +531,7 @@ int ms_conv_block_bwd_ex(const ms_conv_desc* d, const float* x, const float* x2,
     if (side_stream) return set_error("ms_conv_block_bwd: no side-stream form in the 16-bit modes");
     if (d->mode == MS_BARE && out_f32_of(d) && !dyr) return set_error("ms_conv_block_bwd: fp32 dy needs the dyr scratch");
     return block_bwd16(d, x, x2, w, gamma, y_raw, y, save, dy, dyr, dx, dx2, dw, dbias, dgamma, dbeta, workspace, workspace_bytes,
-                       (hipStream_t)stream, wt_prepared, opt->wgrad_partials, opt->defer_wgrad_launch);
+                       (hipStream_t)stream, wt_prepared, opt->wgrad_partials, opt->defer_wgrad_launch, opt->dx_accum);
   }
   const BwdPlan p = bwd_plan(d);
   if (workspace_bytes < p.ws.total) return set_error("ms_conv_block_bwd: workspace too small");
@@ -608,6 +609,8 @@ int ms_conv_block_bwd_ex(const ms_conv_desc* d, const float* x, const float* x2,
       rc = clip32_block_dgrad(d, gr, wp, dx, dx2, s, nullptr, nullptr, nullptr, 0, opt->dx_accum);
     }
     if (rc && rc != -2) return rc;
+    // (the data-gradient paths below know nothing of dx_accum: a decline must not leave dx without it)
+    if (rc == -2 && opt->dx_accum) return set_error("ms_conv_block_bwd: the clip-resident data gradient declined a launch with dx_accum");
     dx_done = rc == 0;
     rc = 0;
   }

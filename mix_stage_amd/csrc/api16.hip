@@ -121,6 +121,13 @@ bool stat_pair16_ok(const ms_conv_desc* d) {
   return (long)d->B / 2 * g.hw <= BN_BWD16_FUSED_MAX;
 }
 
+// The data-gradient launch adds ms_bwd_options.dx_accum itself: plain input (dx is one cb8 tensor of the input's shape -- the upsample-add
+// form writes two, the broadcast form sums the groups), and a kernel for the geometry.  1-D and 2-D, any stride, grouped or not.
+bool dgrad16_takes_accum(const ms_conv_desc* d) {
+  if (dt_of(d) != DT_BF16 && dt_of(d) != DT_F16) return false;
+  return d->in_mode == MS_IN_PLAIN && dgrad_plan16(d).pl.ok != 0;
+}
+
 int block_fwd16(const ms_conv_desc* d, const void* x, const void* x2, const float* w, const float* bias, const float* gamma,
                 const float* beta, float* running_mean, float* running_var, void* y_raw, void* y, float* save, void* workspace,
                 size_t workspace_bytes, hipStream_t s, const void* w_prepared, int32_t* bn_sync, int bn_sync_words) {
@@ -230,7 +237,7 @@ int block_fwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
 int block_bwd16(const ms_conv_desc* d, const void* x, const void* x2, const float* w, const float* gamma, const void* y_raw,
                 const void* y, const float* save, const void* dy, void* dyr, void* dx, void* dx2, float* dw, float* dbias,
                 float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, hipStream_t s, const void* wt_prepared,
-                float* wgrad_partials, int defer_wgrad_launch) {
+                float* wgrad_partials, int defer_wgrad_launch, const void* dx_accum) {
   const BlockGeo g = geo_of(d);
   if (g.dt != DT_BF16 && g.dt != DT_F16) return set_error("ms_conv_block_bwd: dtype %d", d->dtype);
   const Bwd16Layout ws = bwd16_layout(d);
@@ -280,13 +287,16 @@ int block_bwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
     Conv16Args q = {};
     q.A = A; q.src = gsrc; q.out = dx; q.out2 = dx2;
     q.Mg = d->Cin; q.groups = dg.tg; q.Kc8g = c8_of(dg.tcog); q.bcast = 0;
-    q.ep = g.up2 ? EP_DGRAD_UP2 : EP_BARE; q.is_dgrad = 1;
+    // dx_accum: the input's other consumer's gradient (cb8, dx's own layout) joins the fp32 accumulators in the epilogue
+    q.ep = g.up2 ? EP_DGRAD_UP2 : dx_accum ? EP_DGRAD_ACC : EP_BARE; q.is_dgrad = 1;
+    q.acc = dx_accum;
     q.KH = dg.jh; q.S = 1; q.SV = 1;
     fill_src8(q, plane_strides(g.one_d, d->B, g.C8, d->OH, d->OW));
     fill_out8(q, plane_strides(g.one_d, d->B, g.cin8_tot, d->H, d->W));
     const double flops = fill_parity_classes(q, d, dg, g.one_d);
     q.slope = d->slope; q.eps = d->eps;
-    const double bytes = 2.0 * ((double)g.C * d->Cin * d->KH * d->KW + (double)d->B * g.C * g.hw + (double)d->B * g.cin_tot * d->H * d->W);
+    const double bytes = 2.0 * ((double)g.C * d->Cin * d->KH * d->KW + (double)d->B * g.C * g.hw +
+                                (dx_accum ? 2.0 : 1.0) * (double)d->B * g.cin_tot * d->H * d->W);
     rc = launch_conv16(g.dt, q, dg.pl, dg.jw, false, flops, bytes, s);
     if (rc) return rc;
   }

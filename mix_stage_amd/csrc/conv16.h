@@ -30,6 +30,7 @@ struct Conv16Args {
   const void* src2;     // UP2: residual r (full resolution); strides below describe r / the plain input
   void* out;            // cb8
   void* out2;           // EP_DGRAD_UP2: gradient of the residual (cb8)
+  const void* acc;      // EP_DGRAD_ACC: cb8 tensor of `out`'s type and strides, added to the accumulators before the one rounding
   float* out_f32;       // != NULL: plain (B, C, OH, OW) fp32 output instead of `out`
   const float* bias;
   const float* bn_g;
@@ -174,7 +175,8 @@ int block_fwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
 int block_bwd16(const ms_conv_desc* d, const void* x, const void* x2, const float* w, const float* gamma, const void* y_raw,
                 const void* y, const float* save, const void* dy, void* dyr, void* dx, void* dx2, float* dw, float* dbias,
                 float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, hipStream_t s, const void* wt_prepared,
-                float* wgrad_partials, int defer_wgrad_launch);
+                float* wgrad_partials, int defer_wgrad_launch, const void* dx_accum);
+bool dgrad16_takes_accum(const ms_conv_desc* d);      // ms_dgrad_takes_accum for the 16-bit descriptors
 size_t weights16_bytes(const ms_conv_desc* d, int which);
 int wgrad16_splits(const ms_conv_desc* d);
 

@@ -440,6 +440,8 @@ int launch_conv16(int dt, const Conv16Args& a, const Conv16Plan& pl, int KW, boo
   if ((double)b.gx * b.gy * b.gz > 2.0e9) return set_error("conv16: grid too large");
   if ((double)b.a_cls_stride * std::max(1, a.ncls) * 16.0 >= 4.0e9) return set_error("conv16: prepared weights of 4 GB or more");
   if (a.groups > 1 && (a.Mg & 7)) return set_error("conv16: grouped blocks need a multiple of 8 output channels per group");
+  if ((a.ep == EP_DGRAD_ACC) != (a.acc != nullptr) || (a.acc && (up2 || a.out_f32)))
+    return set_error("conv16: the accumulate input belongs to the plain cb8 data gradient (EP_DGRAD_ACC)");
   const int nwg = b.gx * b.gy * b.gz;
   char ring[32] = "";
   if (pl.dma) {
@@ -449,7 +451,7 @@ int launch_conv16(int dt, const Conv16Args& a, const Conv16Plan& pl, int KW, boo
   TimingScope ts(s, flops, bytes, "conv16_kernel<%s,%d,%d,%d,%d,%d,%d>|conv_%s_cb8 k%dx%d s%d Mg%d Kg%d g%d tiles%d tile%dx%d tw%d%s%s",
                  dt == DT_BF16 ? "bf16" : "f16", KW, pl.wm, pl.wn, up2 ? 1 : 0, pl.dma, pl.nwn, a.is_dgrad ? "dgrad" : "fwd", a.KH, KW, a.S, a.Mg,
                  a.Kc8g * 8 * a.KH * KW, a.groups, pl.n_tiles, bm, 32 * pl.wn * pl.nwn, pl.tw, ring,
-                 a.ep == EP_RAW_STATS ? " +bnstats" : a.ep == EP_BN_FUSED ? " +bnfused" : "");
+                 a.ep == EP_RAW_STATS ? " +bnstats" : a.ep == EP_BN_FUSED ? " +bnfused" : a.ep == EP_DGRAD_ACC ? " +acc" : "");
   if (ts.skip()) return 0;
   const int rc = dt == DT_BF16 ? launch_kw<BF16>(b, pl, KW, up2, nwg, s) : launch_kw<F16>(b, pl, KW, up2, nwg, s);
   if (rc) return rc;

@@ -170,6 +170,28 @@ __device__ __forceinline__ void conv16_epilogue(const Conv16Args& p, const f32x1
 #pragma unroll
       for (int q = 0; q < 16; ++q) { s1[q] = 0.f; s2[q] = 0.f; }
     }
+    // The 16-byte slot of `out` that this lane writes for pixel column j and channel-block pair pr of row block i, and whether it is
+    // inside the tensor.  EP_DGRAD_ACC reads `acc` through it as well (acc has out's strides): one guard, one address.
+    const auto out_slot = [&](int j, int pr, size_t& at) -> bool {
+      const int n = (tl.wn * WN + j) * 32 + tl.r;
+      const int oy = tl.oy0 + (n >> p.ltw), ox = tl.ox0 + (n & (TW - 1));
+      const int cb = ((tl.g * p.Mg + tl.m0 + (tl.wm * WM + i) * 32) >> 3) + pr + 2 * tl.h;
+      at = (size_t)tl.img * p.o_img + (size_t)(oy * p.o_sh + tl.o_ry) * p.o_row + (size_t)(ox * p.o_sw + tl.o_rx) + (size_t)cb * p.o_cblk;
+      return ((oy < tl.OUTH) & (ox < tl.OUTW)) && cb < ((tl.g * p.Mg + p.Mg + 7) >> 3);
+    };
+    // EP_DGRAD_ACC: all 2*WN vectors of this row block are requested here, before the first of them is used (one round trip per row
+    // block, not one per store).  Pad channels of dx stay zero because acc's are (include/mixstage.h).
+    u32x4 addv[EP == EP_DGRAD_ACC ? WN : 1][2];
+    if (EP == EP_DGRAD_ACC) {
+#pragma unroll
+      for (int j = 0; j < WN; ++j)
+#pragma unroll
+        for (int pr = 0; pr < 2; ++pr) {
+          size_t at;
+          const bool ok = out_slot(j, pr, at);
+          addv[EP == EP_DGRAD_ACC ? j : 0][pr] = ok ? reinterpret_cast<const u32x4*>(p.acc)[at] : u32x4{0u, 0u, 0u, 0u};
+        }
+    }
 #pragma unroll
     for (int j = 0; j < WN; ++j) {
       const int n = (tl.wn * WN + j) * 32 + tl.r;
@@ -216,6 +238,12 @@ __device__ __forceinline__ void conv16_epilogue(const Conv16Args& p, const f32x1
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr) {
           const int cb = cb_tile + pr + 2 * tl.h;
+          if (EP == EP_DGRAD_ACC) {                    // fp32 sum, then the data gradient's only rounding (pack8 below)
+            float add[8];
+            unpack8<DT>(addv[EP == EP_DGRAD_ACC ? j : 0][pr], add);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) vec[pr][e] += add[e];
+          }
           if (EP == EP_DGRAD_UP2) {
             // 1-D stride-1 data gradient of an upsample-add input: out2 = grad of the residual (full resolution),
             // out = grad of the half-resolution tensor = sum over the pair of columns (adjacent lanes)
@@ -229,8 +257,9 @@ __device__ __forceinline__ void conv16_epilogue(const Conv16Args& p, const f32x1
                 reinterpret_cast<u32x4*>(p.out)[hb + (size_t)cb * (p.o_cblk >> 1)] = pack8<DT>(pair);
               }
             }
-          } else if (cval && cb < cb_end && !(p.dbg & 1)) {
-            reinterpret_cast<u32x4*>(p.out)[obase + (size_t)cb * p.o_cblk] = pack8<DT>(vec[pr]);
+          } else {
+            size_t at;
+            if (out_slot(j, pr, at) && !(p.dbg & 1)) reinterpret_cast<u32x4*>(p.out)[at] = pack8<DT>(vec[pr]);
           }
         }
       }
@@ -815,6 +844,7 @@ __global__ __launch_bounds__(128 * NWN) void conv16_kernel(const Conv16Args p) {
       case EP_BN_EVAL: conv16_epilogue<DT, WM, WN, NWN, EP_BN_EVAL, false>(p, acc, tl, smem, bias_pre); break;
       case EP_RAW_STATS: conv16_epilogue<DT, WM, WN, NWN, EP_RAW_STATS, false>(p, acc, tl, smem, bias_pre); break;
       case EP_BN_FUSED: conv16_epilogue_bnfused<DT, WM, WN, NWN>(p, acc, tl, smem, bias_pre); break;
+      case EP_DGRAD_ACC: conv16_epilogue<DT, WM, WN, NWN, EP_DGRAD_ACC, false>(p, acc, tl, smem, bias_pre); break;
       default: conv16_epilogue<DT, WM, WN, NWN, EP_DGRAD_UP2, false>(p, acc, tl, smem, bias_pre); break;
     }
   }

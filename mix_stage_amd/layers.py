@@ -184,7 +184,7 @@ class ConvNormRelu(nn.Module):
         return y if (was_plain or out_f32) else ops16.to_cb8(y, dt)
       y = ops16.conv_block16(x, self.conv.weight, self.conv.bias, self._geometry(), mode, n.weight, n.bias, n.running_mean,
                              n.running_var, x2=x2, in_mode=in_mode, out_f32=out_f32,
-                             bn_folded=getattr(self, '_bn_folded', False))
+                             bn_folded=getattr(self, '_bn_folded', False), link=link)
       return ops16.from_cb8(y, self.conv.weight.shape[0]) if (was_plain and not out_f32) else y
     if mode == MS_BN_TRAIN and ops.bn_sync_active():
       # data parallel with bn_sync='global': bare conv, then BatchNorm over the batch of ALL ranks (two small collectives)
@@ -284,11 +284,13 @@ class UNet1D(nn.Module):
     residuals = [x]
     # residuals[j] feeds conv1[j] AND, as the residual, conv2[max_depth - 1 - j]: the two gradients meet inside conv1[j]'s
     # data-gradient launch (ops.ResidualLink) instead of in an accumulation launch per level -- unless a hook could be looking
+    # (16-bit modes: only with ops.enable_residual_links16(True))
     links = []
     for i, down in enumerate(self.conv1):
       producer = self.conv1[i - 1] if i else self.pre_downsampling_conv[-1]
       up = self.conv2[self.max_depth - 1 - i]
-      lk = ops.ResidualLink() if (not dt and torch.is_grad_enabled() and not _hooked(producer, down, up)) else None
+      lk = ops.ResidualLink() if ((not dt or ops.residual_links16_active()) and torch.is_grad_enabled()
+                                  and not _hooked(producer, down, up)) else None
       links.append(lk)
       x = down(x, _ms_link=(lk, 'consumer')) if lk is not None else down(x)
       if i < self.max_depth - 1:

@@ -651,6 +651,22 @@ def enable_chain_fusion(on):
   return old
 
 
+# MS_LINK16=1 / enable_residual_links16(True): the UNet's residual links (ResidualLink) in the bf16 / fp16 modes.  Off unless asked
+# for -- measured and dropped, DESIGN 4h: the bf16 G-step is no faster with them than without -- and off with the switch above like
+# the fp32 links.
+_links16 = {'on': os.environ.get('MS_LINK16', '0') == '1'}
+
+
+def enable_residual_links16(on):
+  old = _links16['on']
+  _links16['on'] = bool(on)
+  return old
+
+
+def residual_links16_active():
+  return _links16['on'] and _chain_fusion['on']
+
+
 def conv_block(x, w, bias, geom, mode, gamma=None, beta=None, running_mean=None, running_var=None, x2=None,
                in_mode=MS_IN_PLAIN, chain_prev=False, link=None):
   """One conv block of the path on the HIP kernels (see include/mixstage.h: ms_conv_block_fwd/bwd)."""

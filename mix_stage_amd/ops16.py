@@ -257,7 +257,7 @@ def _prepared16_for(w, d, kind, bn=None):
 # ------------------------------------------------------------------------------------------------
 class _ConvBlock16Fn(torch.autograd.Function):
   @staticmethod
-  def forward(ctx, x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, dt_flags, pre=None):
+  def forward(ctx, x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, dt_flags, pre=None, link=None):
     rm, rv = stats if stats is not None else (None, None)
     _need16(x, x2, w, bias, gamma, beta, rm, rv)
     if not is_cb8(x) or (x2 is not None and not is_cb8(x2)):
@@ -309,6 +309,16 @@ class _ConvBlock16Fn(torch.autograd.Function):
                                        _stream(), ctypes.byref(opt)), 'ms_conv_block_fwd_ex')
     ctx.geom_desc = d
     ctx.mode, ctx.in_mode = mode, in_mode
+    # `link`: (ops.ResidualLink, role) -- the rules of the fp32 twin (ops._ConvBlockFn)
+    ctx.link = None
+    if link is not None and pre is None and not ops.bn_sync_active():
+      lk, role = link
+      if role == 'consumer' and in_mode == MS_IN_PLAIN and x.requires_grad and lib().ms_dgrad_takes_accum(ctypes.byref(d)) \
+          and not (getattr(x, '_backward_hooks', None) or getattr(x, 'retains_grad', False)):
+        lk.armed = True
+        ctx.link = link
+      elif role == 'residual' and in_mode == MS_IN_UP2ADD and lk.armed:
+        ctx.link = link
     ctx.has_bias = bias is not None
     ctx.params = (w, bias, gamma, beta)
     ctx.raw_shape = (B, c8) + sp + (8,)
@@ -353,10 +363,26 @@ class _ConvBlock16Fn(torch.autograd.Function):
     defer_launch = bool(D['on'] and direct_w is True and dw is not None and ops.DEFER_WGRAD_LAUNCH)
     opt = BwdOptions(None, None, 0, wt.data_ptr() if wt is not None else None, part.data_ptr() if part is not None else None,
                      1 if defer_launch else 0)
+    # the gradient the input's other consumer left for this launch (ops.ResidualLink): added to the fp32 accumulators of the data
+    # gradient, which is rounded to 16 bits once
+    acc = None
+    if ctx.link is not None and ctx.link[1] == 'consumer':
+      acc, ctx.link[0].grad = ctx.link[0].grad, None
+      ctx.link[0].taken = True
+      if acc is not None and (not want_dx or tuple(acc.shape) != tuple(x.shape) or acc.dtype != x.dtype):
+        raise RuntimeError('residual link: a residual gradient of shape %s, %s arrived for an input of shape %s, %s (needs grad: %s)' %
+                           (tuple(acc.shape), acc.dtype, tuple(x.shape), x.dtype, want_dx))
+      if acc is not None:
+        acc = acc.contiguous()
+        opt.dx_accum = acc.data_ptr()
+        ops._link_stats['in_launch'] += 1
     check(lib().ms_conv_block_bwd_ex(ctypes.byref(d), _ptr(x), _ptr(x2), _ptr(w), _ptr(gamma), None, None, _ptr(y_raw),
                                      _ptr(y), _ptr(save), _ptr(dy), _ptr(dyr), _ptr(dx), _ptr(dx2), _ptr(dw),
                                      _ptr(dbias), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel(), _stream(),
                                      ctypes.byref(opt)), 'ms_conv_block_bwd_ex')
+    if ctx.link is not None and ctx.link[1] == 'residual' and dx2 is not None and ctx.needs_input_grad[1] and not ctx.link[0].taken:
+      ctx.link[0].grad = dx2                # the consumer's data-gradient launch adds it: autograd gets None for the residual
+      dx2 = None
     if defer_launch:
       D['launches'] += 1
       D['keep'].append((x, x2, dy, dyr, dw, part))
@@ -365,17 +391,20 @@ class _ConvBlock16Fn(torch.autograd.Function):
       D['jobs'].append((part, dw, nsplit))
       ops._queue_deferred_flush()
     return (dx, dx2, None if direct_w else dw, None if direct_b else dbias, None if direct_g else dgamma,
-            None if direct_be else dbeta, None, None, None, None, None, None)
+            None if direct_be else dbeta, None, None, None, None, None, None, None)
 
 
 def conv_block16(x, w, bias, geom, mode, gamma=None, beta=None, running_mean=None, running_var=None, x2=None,
-                 in_mode=MS_IN_PLAIN, out_f32=False, bn_folded=False):
+                 in_mode=MS_IN_PLAIN, out_f32=False, bn_folded=False, link=None):
   """One conv block in the 16-bit mode: x (and x2) cb8, result cb8 -- or plain fp32 (B, C, ...) with out_f32."""
   stats = (running_mean, running_var) if running_mean is not None else None
   flags = MS_DT[x.dtype] | (MS_DT_OUT_F32 if out_f32 else 0) | (MS_DT_BN_FOLDED if (bn_folded and mode == MS_BN_EVAL) else 0)
   if ops.stat_pair_active():
     flags |= MS_DT_STAT_PAIR            # two passes of the module side by side in this batch (ops.stat_pair)
-  return _ConvBlock16Fn.apply(x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, flags)
+  # (the links of the 16-bit modes are on only with ops.enable_residual_links16(True) / MS_LINK16=1;
+  # ops.enable_chain_fusion(False) / MS_CHAIN_BN=0 switches them off together with the fp32 ones)
+  link = link if (link is not None and ops.residual_links16_active() and torch.is_grad_enabled()) else None
+  return _ConvBlock16Fn.apply(x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, flags, None, link)
 
 
 # ------------------------------------------------------------------------------------------------
