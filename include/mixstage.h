@@ -571,6 +571,38 @@ int ms_adam_step_segmented(float* p, const float* g, float* m, float* v, size_t 
                            float lr, float beta1, float beta2, float eps, int32_t* step_state,
                            const int32_t* seg_of_chunk, const int32_t* seg_first_step, float* seg_scratch, int n_seg,
                            void* stream);
+/* ms_adam_step_segmented for gradients that carry a LOSS SCALE (fp16 training): the backward pass was seeded with S instead of
+ * 1, so `g` holds S * gradient and `norm` (ms_sqnorm of g) S * ||gradient||.  One prep launch in place of ms_adam_step_segmented's
+ * un-scales the norm IN PLACE (norm[0] is read and written: the caller reads the true norm), folds 1/S into the clip coefficient
+ * the element pass multiplies every gradient with -- no extra pass over the gradients --, decides whether the step is applied
+ * and moves S; the element pass is ms_adam_step_segmented's own.
+ * loss_scale_state: 8 int32 words on the device, initialised by the caller:
+ *   [0] f32  S, always a power of two                [1] f32  1/S
+ *   [2] i32  consecutive finite steps since S last changed (any non-finite step returns it to 0)
+ *   [3] i32  "overflow skips": steps skipped because the scaled gradients were not finite while S > min_scale
+ *   [4] i32  1 while the LAST step was an overflow skip
+ *   [5..7]   reserved, zero
+ * Rule, with finite = |norm[0]| <= 3e38 on entry:
+ *   finite:      the step is applied (step_state[2] = 0); [2] += 1; if growth_interval > 0 and [2] >= growth_interval and
+ *                S < max_scale: S *= 2, [2] = 0.
+ *   not finite:  the update is skipped as in ms_adam_step_segmented (p, m, v untouched, step_state[2] = 1).  S > min_scale: an
+ *                overflow skip -- S /= 2, [3] += 1, [4] = 1; step_state[3] does NOT move (normal operation, not a bad step).
+ *                S == min_scale: a bad step exactly as in the unscaled path, step_state[3] += 1.
+ *                A raised meeting error word: likewise a bad step, at ANY scale, and S stays -- meeting_words is a device table of
+ *                n_meeting_words device pointers (NULL entries are skipped; NULL / 0: no table) to the error words of the
+ *                in-launch meetings the step's launches used (word 0 of the buffers given as ms_fwd_options.bn_sync and
+ *                ms_chain_tensors.sync).  Such a word is sticky and turns every later launch on its counters to NaN: the cause
+ *                of the non-finite step is the meeting that timed out, not the scale, and the scale must not walk down on it.
+ *                The table is read only when the step is not finite.
+ * A skipped step of either kind advances the step clocks (step_state[0] and with it every segment's step count), as the
+ * unscaled path's refused step does.  growth_interval = 0 and min_scale = max_scale = S: a static scale.
+ * The factors are fixed at 2 and 1/2 so that every rescaling is exact: for fp32 gradients S * g with S = 2^k, neither overflowing
+ * nor underflowing, p, m, v, step_state[0] and norm[0] come out bit-identical to ms_adam_step_segmented on g. */
+int ms_adam_step_segmented_scaled(float* p, const float* g, float* m, float* v, size_t n, float* norm, float max_norm,
+                                  float lr, float beta1, float beta2, float eps, int32_t* step_state,
+                                  const int32_t* seg_of_chunk, const int32_t* seg_first_step, float* seg_scratch, int n_seg,
+                                  int32_t* loss_scale_state, int32_t growth_interval, float min_scale, float max_scale,
+                                  const int32_t* const* meeting_words, int n_meeting_words, void* stream);
 size_t ms_reduce_partials_count(size_t n); /* floats needed in `partials` of ms_sqnorm / ms_l1_mean_fwd */
 
 #ifdef __cplusplus

@@ -1552,6 +1552,16 @@ int launch_colsum_finalize(const float* colpart, float* out, int B, int C, hipSt
   return check_launch("colsum_finalize_kernel");
 }
 
+// the element pass of ms_adam_step_segmented on its own, for a caller that ran a prep kernel of its own (loss_scale.hip)
+int launch_adam_seg(float* p, const float* g, float* m, float* v, size_t n, const int32_t* step_state, const int32_t* seg_of_chunk,
+                    const float* seg_scratch, float beta1, float beta2, float eps, hipStream_t s) {
+  int blocks = (int)std::min<size_t>((n + 1023) / 1024, 2048);
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adam_seg_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, step_state, seg_of_chunk, seg_scratch, beta1, beta2,
+                     eps);
+  return check_launch("adam_seg_kernel");
+}
+
 }  // namespace ms
 
 using namespace ms;

@@ -288,5 +288,8 @@ int launch_bn_bwd(const float* dy, const float* y_raw, const float* y, const flo
 int launch_act_bwd(const float* dy, const float* y, float* dyr, float* colpart, float* dbias, int B, int C, int HW, int mode, float slope, int* fused,
                    hipStream_t s);
 int launch_colsum_finalize(const float* colpart, float* out, int B, int C, hipStream_t s);
+// element pass of the segmented Adam step (elementwise.hip: adam_seg_kernel), behind a prep kernel the caller has launched
+int launch_adam_seg(float* p, const float* g, float* m, float* v, size_t n, const int32_t* step_state, const int32_t* seg_of_chunk,
+                    const float* seg_scratch, float beta1, float beta2, float eps, hipStream_t s);
 
 }  // namespace ms

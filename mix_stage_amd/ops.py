@@ -1406,6 +1406,23 @@ def adam_step_segmented(p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, step_
                                      seg_first.numel(), _stream()), 'ms_adam_step_segmented')
 
 
+def adam_step_segmented_scaled(p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, step_state, seg_of_chunk, seg_first, seg_scratch,
+                               loss_scale_state, growth_interval, min_scale, max_scale, meeting_table=None):
+  """adam_step_segmented on gradients that carry the loss scale S = loss_scale_state word 0 (8 int32 words on the device,
+  include/mixstage.h): `norm` holds the norm of the scaled gradients on entry and the true norm on return; the scale moves.
+  meeting_table: int64 device tensor of addresses of in-launch-meeting error words (0: unused entry), see meeting_table()."""
+  if meeting_table is not None and (meeting_table.dtype != torch.int64 or not meeting_table.is_cuda):
+    raise TypeError('adam_step_segmented_scaled: meeting_table is an int64 device tensor of addresses')
+  if loss_scale_state.dtype != torch.int32 or loss_scale_state.numel() != 8 or not loss_scale_state.is_cuda:
+    raise TypeError('adam_step_segmented_scaled: loss_scale_state is 8 int32 words on the device')
+  check(lib().ms_adam_step_segmented_scaled(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(norm), max_norm, lr, beta1, beta2,
+                                            eps, _ptr(step_state), _ptr(seg_of_chunk), _ptr(seg_first), _ptr(seg_scratch),
+                                            seg_first.numel(), _ptr(loss_scale_state), int(growth_interval), float(min_scale),
+                                            float(max_scale), _ptr(meeting_table) if meeting_table is not None else None,
+                                            meeting_table.numel() if meeting_table is not None else 0, _stream()),
+        'ms_adam_step_segmented_scaled')
+
+
 def selftest_mfma(A, B):
   _need_hip(A, B)
   K = A.shape[1]

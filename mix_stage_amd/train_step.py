@@ -22,6 +22,7 @@ import torch
 import torch.distributed as dist
 
 from . import layers, ops, ops16
+from .loss_scale import LossScaleRule, state_words
 
 _ALIGN = 64  # elements: every parameter starts 256-B aligned inside the flat buffer
 
@@ -88,9 +89,12 @@ def peek_step_decisions(D_prob, thresh_value, thresh_iters, thresh_num_iters, th
 
 
 class FlatAdam:
-  """torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) + clip_grad_norm_(params, max_norm) over flat buffers."""
+  """torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) + clip_grad_norm_(params, max_norm) over flat buffers.
+  loss_scale (fp16 training; None: off, nothing changes): anything loss_scale.LossScaleRule accepts.  The gradients then carry the
+  scale S the backward pass was seeded with (seed()): clip_and_step un-scales the norm, folds 1/S into the clip coefficient and
+  moves S on the device (ms_adam_step_segmented_scaled)."""
 
-  def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0, order_last=(), order_first=()):
+  def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0, order_last=(), order_first=(), loss_scale=None):
     self.params = [p for p in params if p.requires_grad]
     if not self.params:
       raise ValueError('no trainable parameters')
@@ -133,6 +137,15 @@ class FlatAdam:
     self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
     self.partials = torch.zeros(ops.lib().ms_reduce_partials_count(total), dtype=torch.float32, device=dev)
     self.step_state = torch.zeros(4, dtype=torch.int32, device=dev)
+    self.loss_scale = LossScaleRule(loss_scale) if loss_scale is not None else None
+    self.ls_state = None
+    # int64 device table of the addresses of the in-launch meetings' error words (MixStageTrainStep keeps it current): a non-finite
+    # step behind a raised word is a bad step that leaves the scale alone.  None: no meeting is looked at.
+    self.meeting_table = None
+    if self.loss_scale is not None:
+      # 8 device words (include/mixstage.h), written here -- before any capture -- and by the prep kernel from then on
+      self.ls_state = torch.zeros(8, dtype=torch.int32, device=dev)
+      self.set_loss_scale_state(self.loss_scale.initial_state())
     # torch.optim.Adam keeps one step count per parameter, started at the parameter's first gradient (and skips
     # parameters that never had one): segment table for the flat buffer
     seg = torch.empty(total // _ALIGN, dtype=torch.int32)
@@ -178,6 +191,41 @@ class FlatAdam:
     self.host_first = [-1] * len(self.params)
     self.seg_first.fill_(-1)
     self.host_step = 0
+    if self.loss_scale is not None:
+      self.set_loss_scale_state(self.loss_scale.initial_state())
+
+  # ---- loss scaling (fp16 training) --------------------------------------------------------------------------
+  def seed(self):
+    """The backward seed of a step this optimizer applies: the 0-dim fp32 view of the scale word on the device (a captured step
+    reads whatever the previous step's prep kernel left there)."""
+    if self.ls_state is None:
+      raise RuntimeError('FlatAdam.seed(): constructed without loss_scale')
+    return self.ls_state.view(torch.float32)[0]
+
+  def loss_scale_state(self):
+    """dict(scale, good_steps, overflow_skips) -- a synchronising host read.  (Word 4, "the last step was an overflow skip", is not
+    part of it: it describes one step, not the scale.)"""
+    if self.ls_state is None:
+      raise RuntimeError('FlatAdam.loss_scale_state(): constructed without loss_scale')
+    w = self.ls_state.cpu()
+    return dict(scale=float(w.view(torch.float32)[0]), good_steps=int(w[2]), overflow_skips=int(w[3]))
+
+  def set_loss_scale_state(self, d):
+    """Write a state back (what loss_scale_state() returned, e.g. from a checkpoint of the caller's).  Not inside a capture.
+    The scale must be a power of two inside this optimizer's [min, max], the two counts non-negative integers.  The last-step flag
+    (word 4) is not carried: it reads 0 until the next step writes it."""
+    if self.ls_state is None:
+      raise RuntimeError('FlatAdam.set_loss_scale_state(): constructed without loss_scale')
+    rule = self.loss_scale
+    for k in ('good_steps', 'overflow_skips'):
+      if isinstance(d[k], bool) or int(d[k]) != d[k] or not (0 <= int(d[k]) <= 0x7fffffff):
+        raise ValueError('set_loss_scale_state: %s is a non-negative integer, got %r' % (k, d[k]))
+    S = LossScaleRule(dict(init=d['scale'], growth_interval=rule.growth_interval, min=rule.min, max=rule.max)).init
+    f, i = state_words(dict(scale=S, good_steps=int(d['good_steps']), overflow_skips=int(d['overflow_skips'])))
+    host = torch.zeros(8, dtype=torch.int32)
+    host.view(torch.float32)[0:2] = torch.tensor(f, dtype=torch.float32)
+    host[2:8] = torch.tensor(i, dtype=torch.int32)
+    self.ls_state.copy_(host)
 
   def gather_foreign_grads(self):
     """Gradients that did not come through the kernels' write-through: p.grad replaced (model.zero_grad(set_to_none=True)
@@ -198,9 +246,16 @@ class FlatAdam:
     """total_norm = ||g||_2 over all parameters; g *= min(1, max_norm/(norm+1e-6)); Adam update (per-parameter step
     counts).  count=False while a HIP graph is being captured (nothing executes)."""
     ops.grad_norm(self.flat_g, self.norm, self.partials)
-    ops.adam_step_segmented(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm, self.max_norm, self.lr,
-                            self.betas[0], self.betas[1], self.eps, self.step_state, self.seg_of_chunk, self.seg_first,
-                            self.seg_scratch)
+    if self.loss_scale is None:
+      ops.adam_step_segmented(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm, self.max_norm, self.lr,
+                              self.betas[0], self.betas[1], self.eps, self.step_state, self.seg_of_chunk, self.seg_first,
+                              self.seg_scratch)
+    else:
+      # flat_g and norm hold S x the gradients / their norm: un-scaled inside the prep launch (norm in place), S moves there
+      rule = self.loss_scale
+      ops.adam_step_segmented_scaled(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm, self.max_norm, self.lr,
+                                     self.betas[0], self.betas[1], self.eps, self.step_state, self.seg_of_chunk, self.seg_first,
+                                     self.seg_scratch, self.ls_state, rule.growth_interval, rule.min, rule.max, self.meeting_table)
     ops.refresh_prepared_weights(self.flat_p)        # data-gradient weights of all blocks of this network: one launch
     self.seen_version = self._param_versions()
     if count:
@@ -227,7 +282,7 @@ class MixStageTrainStep:
   """Runs reference-equivalent training steps for GAN(G, D) on one GPU or data-parallel over ranks."""
 
   def __init__(self, model, lr=1e-4, clip=1.0, use_graphs=True, process_group=None, time_steps=64, overlap_wgrad=False,
-               bn_sync='local', overlap_allreduce=False, grad_buckets=None, grad_exchange='fp32'):
+               bn_sync='local', overlap_allreduce=False, grad_buckets=None, grad_exchange='fp32', loss_scale=None):
     self.model = model
     if bn_sync not in ('local', 'global'):
       raise ValueError("bn_sync must be 'local' or 'global'")
@@ -236,10 +291,26 @@ class MixStageTrainStep:
     if bn_sync == 'global':
       if not rccl:
         use_graphs = False      # gloo's statistics exchanges (host side) cannot be captured; RCCL's are graph nodes like any kernel
-    if getattr(model, '_ms_dt', 0) == ops16.MS_F16:
-      # loss-mean gradients of ~1/(B*T*P) = 5e-6 sit in the fp16 subnormal range: without a loss scale (not implemented) the
-      # activation gradients underflow.  fp16 is the inference arithmetic (BASELINE configs[4]); train in bf16 or fp32.
-      raise NotImplementedError("training in fp16 needs loss scaling, which this path does not implement: use 'bf16' or 'fp32'")
+    is_f16 = getattr(model, '_ms_dt', 0) == ops16.MS_F16
+    if loss_scale is None:
+      if is_f16:
+        # loss-mean gradients of ~1/(B*T*P) = 5e-6 sit in the fp16 subnormal range: without a loss scale the activation gradients
+        # underflow.  Scaling is opt-in (loss_scale='dynamic'); without it fp16 is the inference arithmetic (BASELINE configs[4]).
+        raise NotImplementedError("training in fp16 needs loss scaling, which is opt-in: pass loss_scale='dynamic', or use 'bf16' or 'fp32'")
+      self.loss_scale_rule = None
+    else:
+      # Dynamic loss scaling (fp16 only): the backward seed of a step is the stepping optimizer's scale S, a device word, instead of
+      # 1; the optimizer's prep launch un-scales the norm, folds 1/S into the clip coefficient and moves S (loss_scale.py).
+      # Loss VALUES stay unscaled -- the forward pass is untouched.  Each network owns its scale: G-step and D-step gradients differ
+      # in magnitude.
+      if not is_f16:
+        raise ValueError('loss_scale is for fp16 models (set_compute_dtype(model, "fp16")): bf16 and fp32 have the exponent range, '
+                         'a scale buys them nothing')
+      if bn_sync == 'global':
+        raise NotImplementedError("fp16 training with bn_sync='global' is not implemented: the statistics exchange has never run in fp16")
+      if _dp_world(process_group) > 1:
+        raise NotImplementedError('fp16 training is single-rank: the data-parallel exchange of scaled gradients is not implemented')
+      self.loss_scale_rule = LossScaleRule(loss_scale)
     self.process_group = process_group
     if grad_exchange not in ('fp32', 'bf16'):
       raise ValueError("grad_exchange must be 'fp32' or 'bf16'")
@@ -285,8 +356,8 @@ class MixStageTrainStep:
     idle = [p for n, p in model.G.named_parameters()
             if n.split('.')[0] in ('text_encoder', 'pose_encoder', 'style_dec', 'style_dec_gr', 'concat_encoder', 'smoothen')]
     early = [p for n, p in model.G.named_parameters() if n.split('.')[0] in ('decoder', 'logits', 'classify_cluster')]
-    self.optim_G = FlatAdam(model.G.parameters(), lr=lr, max_norm=clip, order_last=idle, order_first=early)
-    self.optim_D = FlatAdam(model.D.parameters(), lr=lr, max_norm=clip)
+    self.optim_G = FlatAdam(model.G.parameters(), lr=lr, max_norm=clip, order_last=idle, order_first=early, loss_scale=self.loss_scale_rule)
+    self.optim_D = FlatAdam(model.D.parameters(), lr=lr, max_norm=clip, loss_scale=self.loss_scale_rule)
     self.use_graphs = use_graphs
     self.time_steps = time_steps
     self.pg = process_group
@@ -336,6 +407,14 @@ class MixStageTrainStep:
     self.losses = None       # list of 0-dim device tensors of the last step (reference order)
     # d(sum of losses)/d(loss) = 1: one constant on the default stream, made before any capture or side-stream pass
     self._seed = torch.ones((), dtype=torch.float32, device=self.optim_G.flat_p.device)
+    # ... or, with a loss scale, the stepping optimizer's scale word
+    self._seeds = (self.optim_G.seed(), self.optim_D.seed()) if self.loss_scale_rule is not None else None
+    # ... and the scaled optimizer tail looks at the meetings' error words (a meeting that timed out is a bad step whatever the
+    # scale): one table of their addresses for both optimizers, refreshed on the host when a sync buffer appears (_refresh_meetings)
+    self._meeting_ptrs = None
+    if self.loss_scale_rule is not None:
+      table = torch.zeros(self._MEETING_SLOTS, dtype=torch.int64, device=self.optim_G.flat_p.device)
+      self.optim_G.meeting_table = self.optim_D.meeting_table = table
     self.fake_pose = None
 
   # ---- the eager pieces ------------------------------------------------------------------------------------
@@ -357,11 +436,31 @@ class MixStageTrainStep:
     ops.reset_deferred_wgrad()
     ops.set_backward_overlap(self.side_stream)      # weight gradients on a side stream, joined below
     try:
-      torch.autograd.backward(dev_losses, [self._seed] * len(dev_losses))   # == sum(losses).backward()
+      # (the step kind is the model's draw: known after the forward pass)
+      seed = self._seed if self._seeds is None else self._seeds[0 if m.G_flag else 1]
+      torch.autograd.backward(dev_losses, [seed] * len(dev_losses))   # == sum(losses).backward(), times the loss scale if any
     finally:
       ops.join_backward_overlap()
       ops.set_backward_overlap(None)
     return fake, losses
+
+  _MEETING_SLOTS = 4096    # sync buffers a process may hold (per stream, per chained-decoder shape, per fp32 clip block: a trainer has
+                           # tens; the table covers every buffer of the process, as ops16.bn_sync_error() does)
+
+  def _refresh_meetings(self):
+    """Loss scaling only: the table of error-word addresses follows ops16's sync buffers -- they are created by the first launch that
+    needs one, i.e. during this step's forward pass or its capture.  Called between the forward / backward pass (or the capture,
+    which executes nothing) and the optimizer tail that reads the table; a host-to-device copy only when the set changed."""
+    if self.loss_scale_rule is None:
+      return
+    ptrs = tuple(b.data_ptr() for b in ops16._bn_sync.values())
+    if ptrs != self._meeting_ptrs:
+      if len(ptrs) > self._MEETING_SLOTS:
+        raise RuntimeError('loss scaling: %d in-launch meeting buffers exceed the table of %d' % (len(ptrs), self._MEETING_SLOTS))
+      host = torch.zeros(self._MEETING_SLOTS, dtype=torch.int64)
+      host[:len(ptrs)] = torch.tensor(ptrs, dtype=torch.int64)
+      self.optim_G.meeting_table.copy_(host)
+      self._meeting_ptrs = ptrs
 
   def _with_marker(self, fn, *args):
     """fn(*args) with the backward-pass marker armed (data-parallel G-steps with the overlapped exchange)."""
@@ -467,7 +566,12 @@ class MixStageTrainStep:
     """One training step.  kind=None follows the reference's coin flip (host generator); 'G'/'D' pins it.
     Returns the step kind.  self.losses / self.fake_pose hold device tensors (no host sync here).
     inputs_unchanged=True (graph mode only): the caller promises the four inputs hold the previous step's values, the
-    copies into the captured step's static buffers are skipped."""
+    copies into the captured step's static buffers are skipped.
+    With loss_scale (fp16): a step whose SCALED gradients are not finite while the scale is above its floor is an overflow skip --
+    the weights stay, the scale halves, and it is neither a bad step nor counted in skipped_steps (loss_scale() reports it).  A
+    persistent NaN source in the DATA therefore surfaces as a bad step only once the scale has fallen to its floor: from 2^16 down to
+    1 that is 16 steps of that network, plus the health lag below.  A meeting that timed out is different: its error word is read
+    on the device, the step is a bad step at once and the scale stays where it was."""
     m = self.model
     self._ensure_train_mode()
     # (module-level switch of the ops: another trainer built in this process may have set it differently)
@@ -486,6 +590,7 @@ class MixStageTrainStep:
         active = opt.active_params()
         opt.mark_active(active)
         self._all_reduce(opt, active)
+        self._refresh_meetings()
         opt.clip_and_step()
       else:
         self._graph_step(k, pose_branch, audio, labels, pose, style, inputs_unchanged)
@@ -565,7 +670,10 @@ class MixStageTrainStep:
     (on_bad_step='raise') if a step was refused since the last look -- a launch whose workgroups meet inside the launch (in-launch
     BatchNorm, chained decoder) gave up waiting and poisoned its outputs with NaN, or a gradient was not finite.  Causes of the
     former: another process or a large kernel on another stream held compute units the launch needed -- run one trainer per GPU, or
-    switch the forms off (ops16.set_in_launch_meetings(False))."""
+    switch the forms off (ops16.set_in_launch_meetings(False)).
+    With loss_scale (fp16) overflow skips are normal operation and never raise here; a NaN that stays in the data is reported once
+    the scale has reached its floor (16 halvings from 2^16); a raised meeting error word is reported at once, as without a scale,
+    and does not move the scale, see step()."""
     torch.cuda.synchronize()
     self._health_events = []
     count = int(self.optim_G.step_state[3]) + int(self.optim_D.step_state[3])
@@ -606,6 +714,7 @@ class MixStageTrainStep:
     for mod in entry['bn_tape']:
       mod.__dict__['_pending_batches'] += 1      # (a plain int attribute: nn.Module.__setattr__'s type checks cost 0.6 us each, x 53 blocks)
     opt.mark_active(entry['active'])
+    self._refresh_meetings()
     entry['fwd_bwd'].replay()
     if entry['opt'] is not None:            # (gloo: the exchange runs eagerly between the two graphs)
       self._all_reduce(opt, entry['active'])
@@ -687,6 +796,12 @@ class MixStageTrainStep:
                  n_prepared=ops.prepared_count(opt.flat_p))
     self._graphs[key] = entry
     return entry
+
+  def loss_scale(self):
+    """{'G': dict(scale, good_steps, overflow_skips), 'D': ...} of the two networks' loss scales (synchronises)."""
+    if self.loss_scale_rule is None:
+      raise RuntimeError('MixStageTrainStep.loss_scale(): constructed without loss_scale')
+    return {'G': self.optim_G.loss_scale_state(), 'D': self.optim_D.loss_scale_state()}
 
   def state_checksums(self):
     """(sum, l2) of the flat parameter buffers -- cheap parity probe."""
