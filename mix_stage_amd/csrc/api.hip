@@ -339,10 +339,12 @@ size_t ms_wgrad_partials_elems(const ms_conv_desc* d, int* splits) {
 int ms_wgrad_reduce_multi(int n, const float* const* partials, float* const* dw, const int* elems, const int* splits,
                           void* stream) {
   if (n < 0 || (n && (!partials || !dw || !elems || !splits))) return set_error("ms_wgrad_reduce_multi: null argument");
+  // every job is checked before the first launch: a bad job behind REDUCE_BATCH_MAX good ones must not leave half the call done
+  for (int i = 0; i < n; ++i)
+    if (!partials[i] || !dw[i] || elems[i] <= 0 || splits[i] < 1) return set_error("ms_wgrad_reduce_multi: bad job %d", i);
   ReduceBatch rb;
   rb.n = 0;
   for (int i = 0; i < n; ++i) {
-    if (!partials[i] || !dw[i] || elems[i] <= 0 || splits[i] < 1) return set_error("ms_wgrad_reduce_multi: bad job %d", i);
     ReduceJob jb = {partials[i], dw[i], elems[i], splits[i], 0, 0};
     rb.job[rb.n++] = jb;
     if (rb.n == REDUCE_BATCH_MAX) {

@@ -240,7 +240,10 @@ def reset_deferred_wgrad():
 def _queue_deferred_flush():
   """The queues (here and in the library: wgrad_patch.hip / wgrad16.hip) are process-wide and flushed on ONE stream at the end
   of ONE backward pass: every block that queues work during a backward pass must run on the device and stream of the first
-  one.  (The queued kernels ACCUMULATE into the gradient slots: FlatAdam.zero_grad of the same step is a precondition.)"""
+  one.  (The queued kernels ACCUMULATE into the gradient slots: FlatAdam.zero_grad of the same step is a precondition.)
+  The queue's contract -- every job of a flush computes what it computes alone and what the unqueued launch computes, bit for bit,
+  whatever its place in a job table; writes add; a discarded queue leaves nothing behind -- is checked case by case in
+  tests/test_gpu_wgrad_queue.py (cases: tests/helpers/wgrad_queue_table.py)."""
   owner = (torch.cuda.current_device(), _stream().value)
   if not _deferred['queued']:
     _deferred['queued'] = True

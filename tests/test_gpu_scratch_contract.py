@@ -423,6 +423,26 @@ def _block_float64_bars(blk, x, gy, run, grads, groups, stride, padding):
   assert not bad, 'errors (value, bar): %s' % bad
 
 
+def _block16_float64_bars(blk, x, gy, run, grads, geometry, dt_name):
+  """The 16-bit block against float64 on its 16-bit-rounded operands, slope mask from the device output: the reference and the bars of
+  test_gpu_kernels16._case as helpers/wgrad_queue_checks.py restates them for a block that lives in a module (forward 1.2e-2,
+  gradients 2e-2 in l2 and twice that in max-abs, running statistics 1e-4 / 2e-3)."""
+  import mix_stage_amd as A
+  from helpers import wgrad_queue_checks as C
+  from helpers.wgrad_queue_table import Bk
+  B, cin, cout, groups, k, s, p, T = geometry
+  b = Bk(1, B, cin, cout, groups, k, s, p, (T,), prec=dt_name)
+  fresh = _deterministic(A.ConvNormRelu(cin, cout, type='1d', leaky=True, kernel_size=k, stride=s, padding=p, groups=groups), 'blk.')
+  params = dict(w=blk.conv.weight, bias=blk.conv.bias, gamma=blk.norm.weight, beta=blk.norm.bias)
+  macs = B * groups * cout * cin * k * run['y'].shape[-1]
+  ref = C.reference(b, params, [dict(xs=[x], gy=gy, y=run['y'])], fresh.norm.running_mean, fresh.norm.running_var, dev=DEV if macs > 5e8 else 'cpu')
+  gw, gbias, gg, gb = grads
+  got = dict(y=[run['y']], dx0=[run['dx']], dx1=[None], dw=gw, dbias=gbias, dgamma=gg, dbeta=gb, rm=run['rm'], rv=run['rv'])
+  errs = C.bars(b, got, ref)
+  assert 'dw l2' in errs and 'fwd[0]' in errs and 'running_var' in errs
+  assert not C.failed(errs), 'errors (value, bar): %s' % C.failed(errs)
+
+
 def test_block_with_backward_overlap_on_exact_poisoned_scratch(monkeypatch, trainer_globals_restored):
   """unet_pre's geometry at B = 32 with ops.set_backward_overlap: the weight gradient runs on the side stream with the side
   workspace (ms_conv_block_bwd_overlap), both workspaces exactly sized."""
@@ -452,6 +472,8 @@ def test_trainer_mode_block_on_exact_poisoned_scratch(name, geometry, dt_name, m
   _assert_same_bits(runs, RUN_NAMES, 'trainer-mode ' + name)
   if not dt_name:
     _block_float64_bars(blk, x, gy, runs[2], grads, geometry[3], geometry[5], geometry[6])
+  else:
+    _block16_float64_bars(blk, x, gy, runs[2], grads, geometry, dt_name)
 
 
 # ------------------------------------------------------------------------------------------------ c. loss / optimizer scratch
