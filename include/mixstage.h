@@ -603,6 +603,29 @@ int ms_adam_step_segmented_scaled(float* p, const float* g, float* m, float* v, 
                                   const int32_t* seg_of_chunk, const int32_t* seg_first_step, float* seg_scratch, int n_seg,
                                   int32_t* loss_scale_state, int32_t growth_interval, float min_scale, float max_scale,
                                   const int32_t* const* meeting_words, int n_meeting_words, void* stream);
+/* The two above with the LEARNING RATE AS A DEVICE WORD: `float lr` becomes `const float* lr_dev`, a device pointer to one fp32
+ * word that the prep kernel reads when it RUNS, every other argument is the twin's.  The reference trains with
+ * ExponentialLR(gamma=0.99) stepped once per epoch for both optimizers (TR:311-313,499-500); a step captured into a HIP graph
+ * freezes a by-value lr into every replay, while this form follows whatever the word holds at the replay.
+ *   - for the same lr the results (p, m, v, step_state, seg_scratch; norm and loss_scale_state of the scaled form) are
+ *     bit-identical to the by-value twins: the formulas are one piece of device code;
+ *   - one prep launch and the same element pass: the launch count and the launch label of a step do not change;
+ *   - a word that is NaN, infinite, negative or zero is a BAD STEP exactly as a non-finite gradient norm is: step_state[2] = 1,
+ *     step_state[3] += 1, p, m and v untouched, the step clocks advance.  In the scaled form the loss scale and its counters stay
+ *     where they are (it is not the scale's doing), whatever the gradients were;
+ *   - lr_dev == NULL is an error and launches nothing; the rest is checked as the twin checks it.
+ * ORDERING RULE: write the word (ms_write_floats: by value through a kernel's arguments) on the SAME stream as the steps, or
+ * graph replays, that are to read it, between two steps.  Stream order then places the write behind every earlier step and in
+ * front of every later one; a host that runs ahead of the device cannot overwrite a value the device has not read yet. */
+int ms_adam_step_segmented_lr(float* p, const float* g, float* m, float* v, size_t n, const float* norm, float max_norm,
+                              const float* lr_dev, float beta1, float beta2, float eps, int32_t* step_state,
+                              const int32_t* seg_of_chunk, const int32_t* seg_first_step, float* seg_scratch, int n_seg,
+                              void* stream);
+int ms_adam_step_segmented_scaled_lr(float* p, const float* g, float* m, float* v, size_t n, float* norm, float max_norm,
+                                     const float* lr_dev, float beta1, float beta2, float eps, int32_t* step_state,
+                                     const int32_t* seg_of_chunk, const int32_t* seg_first_step, float* seg_scratch, int n_seg,
+                                     int32_t* loss_scale_state, int32_t growth_interval, float min_scale, float max_scale,
+                                     const int32_t* const* meeting_words, int n_meeting_words, void* stream);
 size_t ms_reduce_partials_count(size_t n); /* floats needed in `partials` of ms_sqnorm / ms_l1_mean_fwd */
 
 #ifdef __cplusplus

@@ -1316,8 +1316,8 @@ __global__ void adam_prep_seg_kernel(int32_t* state, const float* norm, float ma
     float ss = 0.f, b2 = 0.f;
     if (first >= 1 && first <= step) {
       const double t = (double)(step - first + 1);
-      ss = (float)((double)lr / (1.0 - pow((double)beta1, t)));
-      b2 = (float)sqrt(1.0 - pow((double)beta2, t));
+      ss = adam_seg_step_size(lr, beta1, t);      // (kernels.h: one definition for every prep kernel of this step)
+      b2 = adam_seg_bc2(beta2, t);
     }
     seg_scratch[2 * sidx] = ss;
     seg_scratch[2 * sidx + 1] = b2;
@@ -1327,15 +1327,15 @@ __global__ void adam_prep_seg_kernel(int32_t* state, const float* norm, float ma
     state[0] = step;
     float coef = 1.f;
     if (norm) {
-      coef = max_norm / (norm[0] + 1e-6f);
-      if (coef > 1.f) coef = 1.f;
+      // (clip coefficient and health words: kernels.h, shared with the prep kernels of loss_scale.hip and lr_device.hip)
+      coef = adam_clip_coef(max_norm, norm[0]);
       // A non-finite gradient norm (a launch whose in-launch meeting timed out poisons its output with NaN, and the NaN reaches
       // every gradient behind it) must not reach the weights or the moments: the update of this step is SKIPPED on the device --
       // word 2 flags the step, word 3 counts such steps (MixStageTrainStep reads both with the losses); the step clocks advance
       // as if the step had had a zero gradient and frozen moments.
-      const bool bad = !(fabsf(norm[0]) <= 3.0e38f);
-      state[2] = bad ? 1 : 0;
-      if (bad) state[3] += 1;
+      // (a learning rate that is a device word can refuse the step as well: lr_device.hip)
+      const bool bad = !adam_norm_finite(norm[0]);
+      adam_flag_step(state, bad);
     }
     reinterpret_cast<float*>(state)[1] = coef;
   }

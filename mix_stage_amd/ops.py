@@ -1426,6 +1426,49 @@ def adam_step_segmented_scaled(p, g, m, v, norm, max_norm, lr, beta1, beta2, eps
         'ms_adam_step_segmented_scaled')
 
 
+def _check_lr_word(lr_word, who):
+  if not (torch.is_tensor(lr_word) and lr_word.is_cuda and lr_word.dtype == torch.float32 and lr_word.numel() == 1):
+    raise TypeError('%s: lr_word is one fp32 word on the device' % who)
+
+
+def adam_step_segmented_lr(p, g, m, v, norm, max_norm, lr_word, beta1, beta2, eps, step_state, seg_of_chunk, seg_first, seg_scratch):
+  """adam_step_segmented with the learning rate read from `lr_word` (1-element fp32 device tensor) when the prep kernel runs: a
+  captured step follows the word from replay to replay.  Same bits as adam_step_segmented for the same lr."""
+  _check_lr_word(lr_word, 'adam_step_segmented_lr')
+  check(lib().ms_adam_step_segmented_lr(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(norm), max_norm, _ptr(lr_word), beta1,
+                                        beta2, eps, _ptr(step_state), _ptr(seg_of_chunk), _ptr(seg_first), _ptr(seg_scratch),
+                                        seg_first.numel(), _stream()), 'ms_adam_step_segmented_lr')
+
+
+def adam_step_segmented_scaled_lr(p, g, m, v, norm, max_norm, lr_word, beta1, beta2, eps, step_state, seg_of_chunk, seg_first,
+                                  seg_scratch, loss_scale_state, growth_interval, min_scale, max_scale, meeting_table=None):
+  """adam_step_segmented_scaled with the learning rate read from `lr_word`, see adam_step_segmented_lr."""
+  _check_lr_word(lr_word, 'adam_step_segmented_scaled_lr')
+  if meeting_table is not None and (meeting_table.dtype != torch.int64 or not meeting_table.is_cuda):
+    raise TypeError('adam_step_segmented_scaled_lr: meeting_table is an int64 device tensor of addresses')
+  if loss_scale_state.dtype != torch.int32 or loss_scale_state.numel() != 8 or not loss_scale_state.is_cuda:
+    raise TypeError('adam_step_segmented_scaled_lr: loss_scale_state is 8 int32 words on the device')
+  check(lib().ms_adam_step_segmented_scaled_lr(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(norm), max_norm, _ptr(lr_word),
+                                               beta1, beta2, eps, _ptr(step_state), _ptr(seg_of_chunk), _ptr(seg_first),
+                                               _ptr(seg_scratch), seg_first.numel(), _ptr(loss_scale_state), int(growth_interval),
+                                               float(min_scale), float(max_scale),
+                                               _ptr(meeting_table) if meeting_table is not None else None,
+                                               meeting_table.numel() if meeting_table is not None else 0, _stream()),
+        'ms_adam_step_segmented_scaled_lr')
+
+
+def write_floats(dst, values):
+  """Up to 8 host floats -> the fp32 device tensor `dst`, BY VALUE through a kernel's arguments on the current stream
+  (ms_write_floats): the values are copied when the launch is enqueued, so a host that runs ahead of the device cannot overwrite
+  a value the device has not read yet."""
+  vals = [float(x) for x in values]
+  if not (dst.is_cuda and dst.dtype == torch.float32 and dst.is_contiguous() and 1 <= len(vals) <= min(8, dst.numel())):
+    raise TypeError('write_floats: 1..8 values into a contiguous fp32 device tensor that holds them')
+  arr = (ctypes.c_float * len(vals))(*vals)
+  with torch.cuda.device(dst.device):
+    check(lib().ms_write_floats(_ptr(dst), arr, len(vals), _stream()), 'ms_write_floats')
+
+
 def selftest_mfma(A, B):
   _need_hip(A, B)
   K = A.shape[1]

@@ -15,6 +15,7 @@ MI355X-first structure:
     (bn_sync='local'); host-side random decisions come from identically seeded CPU generators so all
     ranks take the same D-vs-G branch (gan.py:105) and curriculum branch (JL:127).
 """
+import copy
 import os
 import weakref
 
@@ -23,6 +24,7 @@ import torch.distributed as dist
 
 from . import layers, ops, ops16
 from .loss_scale import LossScaleRule, state_words
+from .lr_schedule import as_lr_schedule, check_lr
 
 _ALIGN = 64  # elements: every parameter starts 256-B aligned inside the flat buffer
 
@@ -92,9 +94,14 @@ class FlatAdam:
   """torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) + clip_grad_norm_(params, max_norm) over flat buffers.
   loss_scale (fp16 training; None: off, nothing changes): anything loss_scale.LossScaleRule accepts.  The gradients then carry the
   scale S the backward pass was seeded with (seed()): clip_and_step un-scales the norm, folds 1/S into the clip coefficient and
-  moves S on the device (ms_adam_step_segmented_scaled)."""
+  moves S on the device (ms_adam_step_segmented_scaled).
+  device_lr=True: the learning rate lives in `lr_word`, one fp32 word on the device that the prep kernel reads when it runs
+  (ms_adam_step_segmented_lr / _scaled_lr), so a step captured into a HIP graph follows set_lr() from replay to replay.  With
+  False (default) lr is a by-value kernel argument: assigning `self.lr` works for eager launches only, a captured step keeps the
+  value it was captured with."""
 
-  def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0, order_last=(), order_first=(), loss_scale=None):
+  def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0, order_last=(), order_first=(), loss_scale=None,
+               device_lr=False):
     self.params = [p for p in params if p.requires_grad]
     if not self.params:
       raise ValueError('no trainable parameters')
@@ -134,6 +141,13 @@ class FlatAdam:
         p._ms_grad_fresh = False
         self._grad_views.append(g)
     self.lr, self.betas, self.eps, self.max_norm = lr, betas, eps, max_norm
+    self.device_lr = bool(device_lr)
+    self.lr_word = None
+    if self.device_lr:
+      # written here -- before any capture -- and by set_lr() from then on
+      self.lr = check_lr(lr, 'FlatAdam(lr=)')
+      self.lr_word = torch.zeros(1, dtype=torch.float32, device=dev)
+      ops.write_floats(self.lr_word, [self.lr])
     self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
     self.partials = torch.zeros(ops.lib().ms_reduce_partials_count(total), dtype=torch.float32, device=dev)
     self.step_state = torch.zeros(4, dtype=torch.int32, device=dev)
@@ -186,7 +200,25 @@ class FlatAdam:
         self.host_first[i] = self.host_step + 1
       self.seg_first.copy_(torch.tensor(self.host_first, dtype=torch.int32), non_blocking=False)
 
+  def set_lr(self, lr):
+    """The learning rate of the steps from here on.  device_lr=True: the word is written BY VALUE through a kernel's arguments
+    (ms_write_floats) on the current stream -- the stream the steps / replays run on, which orders the write behind every earlier
+    step and in front of every later one, and a host that runs ahead of the replays cannot overwrite a value the device has not
+    read yet (the reason GAN.write_lambdas gives).  Nothing is launched when the value is unchanged.  Not inside a capture."""
+    if not self.device_lr:
+      self.lr = float(lr)          # (a by-value kernel argument: honoured by eager launches, frozen into a captured step)
+      return
+    lr = check_lr(lr, 'FlatAdam.set_lr')
+    if torch.cuda.is_current_stream_capturing():
+      raise RuntimeError('FlatAdam.set_lr inside a stream capture: the write would become part of the captured step')
+    if lr == self.lr:
+      return
+    ops.write_floats(self.lr_word, [lr])
+    self.lr = lr
+
   def reset_state(self):
+    """Moments, step clocks and (fp16) the loss scale back to their initial values.  The learning rate stays: it is a
+    hyper-parameter, not optimizer state."""
     self.exp_avg.zero_(); self.exp_avg_sq.zero_(); self.step_state.zero_()
     self.host_first = [-1] * len(self.params)
     self.seg_first.fill_(-1)
@@ -246,16 +278,20 @@ class FlatAdam:
     """total_norm = ||g||_2 over all parameters; g *= min(1, max_norm/(norm+1e-6)); Adam update (per-parameter step
     counts).  count=False while a HIP graph is being captured (nothing executes)."""
     ops.grad_norm(self.flat_g, self.norm, self.partials)
+    # device_lr: the same launches with lr read from the device word (same bits for the same lr)
+    lr = self.lr_word if self.device_lr else self.lr
     if self.loss_scale is None:
-      ops.adam_step_segmented(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm, self.max_norm, self.lr,
-                              self.betas[0], self.betas[1], self.eps, self.step_state, self.seg_of_chunk, self.seg_first,
-                              self.seg_scratch)
+      (ops.adam_step_segmented_lr if self.device_lr else ops.adam_step_segmented)(
+          self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm, self.max_norm, lr,
+          self.betas[0], self.betas[1], self.eps, self.step_state, self.seg_of_chunk, self.seg_first,
+          self.seg_scratch)
     else:
       # flat_g and norm hold S x the gradients / their norm: un-scaled inside the prep launch (norm in place), S moves there
       rule = self.loss_scale
-      ops.adam_step_segmented_scaled(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm, self.max_norm, self.lr,
-                                     self.betas[0], self.betas[1], self.eps, self.step_state, self.seg_of_chunk, self.seg_first,
-                                     self.seg_scratch, self.ls_state, rule.growth_interval, rule.min, rule.max, self.meeting_table)
+      (ops.adam_step_segmented_scaled_lr if self.device_lr else ops.adam_step_segmented_scaled)(
+          self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm, self.max_norm, lr,
+          self.betas[0], self.betas[1], self.eps, self.step_state, self.seg_of_chunk, self.seg_first,
+          self.seg_scratch, self.ls_state, rule.growth_interval, rule.min, rule.max, self.meeting_table)
     ops.refresh_prepared_weights(self.flat_p)        # data-gradient weights of all blocks of this network: one launch
     self.seen_version = self._param_versions()
     if count:
@@ -279,11 +315,19 @@ class FlatAdam:
 
 
 class MixStageTrainStep:
-  """Runs reference-equivalent training steps for GAN(G, D) on one GPU or data-parallel over ranks."""
+  """Runs reference-equivalent training steps for GAN(G, D) on one GPU or data-parallel over ranks.
+  lr_schedule (None: the learning rate is the constant `lr`, as a by-value kernel argument): a float gamma -- the reference's
+  ExponentialLR(gamma), TR:311-313 -- or a schedule object (lr_schedule.py).  Both optimizers then keep their learning rate in a
+  device word that the captured steps read at every replay; epoch_end() steps the schedule (TR:499-500), set_lr() sets explicit
+  values.  Every rank of a data-parallel job computes the same host values, nothing is exchanged."""
 
   def __init__(self, model, lr=1e-4, clip=1.0, use_graphs=True, process_group=None, time_steps=64, overlap_wgrad=False,
-               bn_sync='local', overlap_allreduce=False, grad_buckets=None, grad_exchange='fp32', loss_scale=None):
+               bn_sync='local', overlap_allreduce=False, grad_buckets=None, grad_exchange='fp32', loss_scale=None, lr_schedule=None):
     self.model = model
+    # one scheduler per optimizer, as in the reference (TR:311-313): each is chained on its own network's learning rate
+    sched = as_lr_schedule(lr_schedule)
+    self.lr_schedules = (sched, copy.deepcopy(sched)) if sched is not None else None
+    self.lr_epoch = 0
     if bn_sync not in ('local', 'global'):
       raise ValueError("bn_sync must be 'local' or 'global'")
     self.bn_sync = bn_sync
@@ -356,8 +400,10 @@ class MixStageTrainStep:
     idle = [p for n, p in model.G.named_parameters()
             if n.split('.')[0] in ('text_encoder', 'pose_encoder', 'style_dec', 'style_dec_gr', 'concat_encoder', 'smoothen')]
     early = [p for n, p in model.G.named_parameters() if n.split('.')[0] in ('decoder', 'logits', 'classify_cluster')]
-    self.optim_G = FlatAdam(model.G.parameters(), lr=lr, max_norm=clip, order_last=idle, order_first=early, loss_scale=self.loss_scale_rule)
-    self.optim_D = FlatAdam(model.D.parameters(), lr=lr, max_norm=clip, loss_scale=self.loss_scale_rule)
+    self.optim_G = FlatAdam(model.G.parameters(), lr=lr, max_norm=clip, order_last=idle, order_first=early, loss_scale=self.loss_scale_rule,
+                            device_lr=self.lr_schedules is not None)
+    self.optim_D = FlatAdam(model.D.parameters(), lr=lr, max_norm=clip, loss_scale=self.loss_scale_rule,
+                            device_lr=self.lr_schedules is not None)
     self.use_graphs = use_graphs
     self.time_steps = time_steps
     self.pg = process_group
@@ -571,7 +617,10 @@ class MixStageTrainStep:
     the weights stay, the scale halves, and it is neither a bad step nor counted in skipped_steps (loss_scale() reports it).  A
     persistent NaN source in the DATA therefore surfaces as a bad step only once the scale has fallen to its floor: from 2^16 down to
     1 that is 16 steps of that network, plus the health lag below.  A meeting that timed out is different: its error word is read
-    on the device, the step is a bad step at once and the scale stays where it was."""
+    on the device, the step is a bad step at once and the scale stays where it was.
+    With lr_schedule: the step reads its optimizer's learning-rate word when it runs.  ORDERING RULE: epoch_end() / set_lr() write
+    the words on the caller's current stream, the stream step() launches or replays on -- call them between two steps, from the
+    thread and under the stream that calls step(); stream order does the rest (no synchronisation)."""
     m = self.model
     self._ensure_train_mode()
     # (module-level switch of the ops: another trainer built in this process may have set it differently)
@@ -796,6 +845,58 @@ class MixStageTrainStep:
                  n_prepared=ops.prepared_count(opt.flat_p))
     self._graphs[key] = entry
     return entry
+
+  # ---- learning rate ------------------------------------------------------------------------------------------
+  def _lr_settable(self, who):
+    if self.lr_schedules is None and self.use_graphs:
+      raise RuntimeError('MixStageTrainStep.%s: this trainer replays captured steps with the learning rate frozen into them; construct '
+                         'it with lr_schedule= (a gamma, a schedule object, or lr_schedule.ConstantLR() for explicit set_lr calls) '
+                         'to keep the learning rate in a device word, or with use_graphs=False' % who)
+
+  def set_lr(self, G=None, D=None):
+    """Explicit learning rates for the two networks (None: leave that one alone).  Between steps, see step().  Without
+    lr_schedule it works on an eager trainer (the launches take the host value) and raises on one that replays graphs."""
+    self._lr_settable('set_lr')
+    if G is not None:
+      self.optim_G.set_lr(G)
+    if D is not None:
+      self.optim_D.set_lr(D)
+
+  def epoch_end(self):
+    """The reference's scheduler.step() at the end of an epoch (TR:499-500): steps the schedule once for each optimizer and
+    writes both learning-rate words.  Between steps, see step().  Returns lr().  Without lr_schedule: counts the epoch on an
+    eager trainer, raises on one that replays graphs."""
+    self._lr_settable('epoch_end')
+    self.lr_epoch += 1
+    if self.lr_schedules is not None:
+      for sched, opt in zip(self.lr_schedules, (self.optim_G, self.optim_D)):
+        opt.set_lr(sched.step(opt.lr))
+    return self.lr()
+
+  def lr(self):
+    """(lr_G, lr_D): the host's values, i.e. what the steps issued from now on use.  Does not synchronise."""
+    return (self.optim_G.lr, self.optim_D.lr)
+
+  def lr_state(self):
+    """dict(epoch, lr_G, lr_D, schedule) for a caller that checkpoints; set_lr_state() restores it."""
+    st = None
+    if self.lr_schedules is not None:
+      st = tuple(s.state() if hasattr(s, 'state') else () for s in self.lr_schedules)
+    return dict(epoch=self.lr_epoch, lr_G=self.optim_G.lr, lr_D=self.optim_D.lr, schedule=st)
+
+  def set_lr_state(self, d):
+    """Restore what lr_state() returned (on a trainer built with the same lr_schedule).  Between steps, see step()."""
+    self._lr_settable('set_lr_state')
+    if (d['schedule'] is None) != (self.lr_schedules is None):
+      raise ValueError('set_lr_state: the state was taken from a trainer %s lr_schedule, this one is built %s'
+                       % (('without', 'with') if d['schedule'] is None else ('with', 'without')))
+    if self.lr_schedules is not None:
+      for s, st in zip(self.lr_schedules, d['schedule']):
+        if hasattr(s, 'set_state'):
+          s.set_state(st)
+    self.lr_epoch = int(d['epoch'])
+    self.optim_G.set_lr(d['lr_G'])
+    self.optim_D.set_lr(d['lr_D'])
 
   def loss_scale(self):
     """{'G': dict(scale, good_steps, overflow_skips), 'D': ...} of the two networks' loss scales (synchronises)."""
