@@ -486,6 +486,19 @@ int ms_concat_style_fwd(const float* x, const float* emb, const int64_t* ids, in
 int ms_concat_style_bwd(const float* dout, const int64_t* ids, int ids_stride_b, int ids_stride_t, float* dx, float* demb,
                         int B, int C, int D, int T, int S, void* stream);
 
+/* Style mixing: the same concat with a float weight per style in place of an id (EmbLin 'lin' mode, x.matmul(emb.weight) +
+ * transpose + torch.cat, layers.py:659-663, JL:159-180): out (B, C+D, T) = [x (B,C,T) ; sum_s w[b,t,s] * E[s] (D)].  w is
+ * addressed as w[b*w_stride_b + t*w_stride_t + s] (strides in elements, last axis contiguous; w_stride_t = 0: one weight row
+ * per clip); rows are used as given, not normalised.  The sum runs in fp32 from zero in ascending s, one fma per term: a
+ * one-hot row returns the embedding row bit for bit, and every result is reproducible bit for bit (no atomics).
+ * bwd: dx (B,C,T) = dout[:, :C];  dE (S,D) = sum_{b,t} w[b,t,s] * dout[b,C+j,t];  dw = sum_j dout[b,C+j,t] * E[s][j], written
+ * as contiguous (B,T,S), or -- w_stride_t = 0 -- summed over t as contiguous (B,S).  NULL = skip.
+ * Refused: S < 1, D < 1, negative strides, S > 65535. */
+int ms_concat_style_soft_fwd(const float* x, const float* emb, const float* w, int w_stride_b, int w_stride_t, float* out,
+                             int B, int C, int D, int T, int S, void* stream);
+int ms_concat_style_soft_bwd(const float* dout, const float* emb, const float* w, int w_stride_b, int w_stride_t, float* dx,
+                             float* demb, float* dw, int B, int C, int D, int T, int S, void* stream);
+
 /* Cross entropy with mean reduction (JL:159,184,203): score addressed as
  * score[n_outer*stride_outer + c*stride_c + n_inner*stride_inner], rows = n_outer*n_inner.
  * loss[0] = mean_rows( logsumexp - score[target] ).  dscore (same addressing) = gscale[0] *

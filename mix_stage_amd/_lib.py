@@ -120,6 +120,8 @@ SIGNATURES = {
     'ms_eval_accumulate': (c_int, [_P] * 8 + [c_int, c_int, c_int, c_int, ctypes.c_double, c_int, _P]),
     'ms_concat_style_fwd': (c_int, [_P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P]),
     'ms_concat_style_bwd': (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    'ms_concat_style_soft_fwd': (c_int, [_P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    'ms_concat_style_soft_bwd': (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     'ms_cross_entropy_fwd': (c_int, [_P, _P, _P, _P] + [c_int] * 6 + [_P]),
     'ms_cross_entropy_bwd': (c_int, [_P, _P, _P, _P] + [c_int] * 7 + [_P]),
     'ms_cross_entropy_fwd_ex': (c_int, [_P, _P, _P] + [c_int] * 6 + [_P, _P]),

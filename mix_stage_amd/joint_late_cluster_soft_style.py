@@ -151,13 +151,19 @@ class JointLateClusterSoftStyle4_G(nn.Module):
         if self.argmax:                                         # which repeats identical rows (JL:160-165)
           pose_style = torch.argmax(pose_style, dim=-1).unsqueeze(1).expand(B, T)
           mode = 'emb'
-        else:
+        elif not ops.style_soft_active():
           pose_style = pose_style.unsqueeze(1).expand(B, T, pose_style.shape[-1])
+      elif ops.style_soft_active():
+        pose_style = pose_style_score                           # (B, S): the mixing kernel takes one weight row per clip
       else:
         pose_style = pose_style_score.unsqueeze(1).expand(B, T, pose_style_score.shape[-1])
     else:
       pose_style = style
-      if len(style.shape) == 2:
+      if style.is_floating_point():
+        mode = 'lin'                                            # per-style weights: (B,T,S), (B,S) or windows of a long sequence
+        if style.dim() == 2 and not ops.style_soft_active():
+          pose_style = style.unsqueeze(1).expand(B, T, style.shape[-1])
+      elif len(style.shape) == 2:
         mode = 'emb'
       elif len(style.shape) == 3:
         mode = 'lin'
@@ -170,6 +176,14 @@ class JointLateClusterSoftStyle4_G(nn.Module):
       ## content || style embedding, channel-major, one kernel (JL:175-180)
       self.pose_style_ids = pose_style
       x = ops.concat_style(x, self.style_emb.emb.weight, pose_style)      # (B, 256+style_dim, T)
+    elif mode == 'lin' and ops.style_soft_active():
+      ## content || weighted mix of the style embeddings, channel-major, one kernel (EmbLin 'lin' + cat, JL:159-180)
+      S = self.style_emb.num_embeddings
+      if pose_style.dim() != 2 and pose_style.shape != (B, T, S) and pose_style.shape[-1] == S and pose_style.numel() == B * T * S:
+        pose_style = pose_style.reshape(B, T, S)               # windows concatenated into one long sequence, as for the ids
+      if pose_style.dtype != x.dtype:
+        pose_style = pose_style.to(x.dtype)                    # (.double() models go through the op's float64 boundary)
+      x = ops.concat_style_soft(x, self.style_emb.emb.weight, pose_style)  # (B, 256+style_dim, T)
     else:
       labels_style = self.style_emb(pose_style, mode=mode)     # (B, T, style_dim)
       if labels_style.shape[1] != T:

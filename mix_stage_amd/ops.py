@@ -1176,6 +1176,73 @@ def concat_style(x, emb_weight, ids):
   return _ConcatStyleFn.apply(x, emb_weight, ids)
 
 
+# MS_STYLE_SOFT=0 / enable_style_soft(False): float style weights (EmbLin 'lin' mode) take the route they took before the
+# mixing kernel existed -- torch's matmul, transpose and cat -- for A/B runs
+_style_soft = {'on': os.environ.get('MS_STYLE_SOFT', '1') != '0'}
+
+
+def enable_style_soft(on):
+  old = _style_soft['on']
+  _style_soft['on'] = bool(on)
+  return old
+
+
+def style_soft_active():
+  return _style_soft['on']
+
+
+class _ConcatStyleSoftFn(torch.autograd.Function):
+  @staticmethod
+  def forward(ctx, x, emb, w):
+    if not isinstance(w, torch.Tensor) or not w.is_cuda or w.dtype != torch.float32 or w.dim() not in (2, 3):
+      raise TypeError('style weights must be a float32 (B,S) or (B,T,S) tensor on the device (expanded and sliced views are fine)')
+    _need_hip(x, emb)
+    x, emb = x.contiguous(), emb.contiguous()
+    B, C, T = x.shape
+    S, D = emb.shape
+    if w.shape != ((B, S) if w.dim() == 2 else (B, T, S)):
+      raise TypeError('style weights of shape %s do not fit B=%d T=%d S=%d' % (tuple(w.shape), B, T, S))
+    if S > 1 and w.stride(-1) != 1:
+      raise TypeError('style weights need unit stride on their last axis (got strides %s)' % (w.stride(),))
+    if max(w.stride()) >= 2 ** 31:
+      raise TypeError('style weight strides %s do not fit the 32-bit strides of the kernel' % (w.stride(),))
+    sb = w.stride(0) if B > 1 else 0
+    st = w.stride(1) if w.dim() == 3 and T > 1 else 0
+    if w.dim() == 3 and T > 1 and st == 0 and w.requires_grad:
+      raise TypeError('per-frame style weights that repeat one row (stride 0 over T) and need a gradient: pass the (B,S) tensor')
+    out = torch.empty((B, C + D, T), dtype=torch.float32, device=x.device)
+    check(lib().ms_concat_style_soft_fwd(_ptr(x), _ptr(emb), _ptr(w), sb, st, _ptr(out), B, C, D, T, S, _stream()),
+          'ms_concat_style_soft_fwd')
+    ctx.save_for_backward(emb, w)
+    ctx.dims = (B, C, D, T, S, sb, st)
+    ctx.emb_param = emb
+    return out
+
+  @staticmethod
+  def backward(ctx, dout):
+    emb, w = ctx.saved_tensors
+    B, C, D, T, S, sb, st = ctx.dims
+    dout = dout.contiguous()
+    dx = torch.empty((B, C, T), dtype=torch.float32, device=dout.device) if ctx.needs_input_grad[0] else None
+    demb, direct = (None, False)
+    if ctx.needs_input_grad[1]:
+      demb, direct = _grad_slot(ctx.emb_param, ctx.emb_param)
+    dw = torch.empty(w.shape, dtype=torch.float32, device=dout.device) if ctx.needs_input_grad[2] else None   # (B,S): summed over t
+    check(lib().ms_concat_style_soft_bwd(_ptr(dout), _ptr(emb), _ptr(w), sb, st, _ptr(dx), _ptr(demb), _ptr(dw), B, C, D, T, S,
+                                         _stream()), 'ms_concat_style_soft_bwd')
+    return dx, None if direct else demb, dw
+
+
+@_bridge64
+def concat_style_soft(x, emb_weight, w):
+  """(B, C+D, T) = [x ; (w @ emb_weight)^T]: EmbLin 'lin' mix + cat of JL:159-180, channel-major.  w: float32 style weights,
+  (B,S) = one row per clip or (B,T,S) = one row per frame, used as given (not normalised); a one-hot row equals concat_style
+  on its id bit for bit.  Gradients for x, emb_weight and w (in w's shape)."""
+  if isinstance(w, torch.Tensor) and w.dim() == 3 and w.shape[1] > 1 and w.stride(1) == 0 and w.requires_grad:
+    w = w[:, 0]                  # one row per clip behind an expand: the kernels sum its gradient over t themselves
+  return _ConcatStyleSoftFn.apply(x, emb_weight, w)
+
+
 def _loss_scale(scale):
   """struct ms_loss_scale for a host constant or a one-float device tensor."""
   if torch.is_tensor(scale):
