@@ -157,12 +157,19 @@ int ms_conv_block_fwd_ex(const ms_conv_desc* d, const float* x, const float* x2,
  * stays allocated until the launch that carries it (or the flush) has been issued.  ms_clip_hold_flush launches a
  * held block now (and disarms); ms_clip_hold_discard drops it (error paths).  ms_clip_hold while a block is pending is an error.
  * ms_clip_grid: workgroups of d's forward launch on the clip-resident kernel, 0 where d does not run there.
- * ms_clip_pair_ok: 1 when block `guest`, held, would share block `host`'s launch on the current device. */
+ * ms_clip_pair_ok: 1 when block `guest`, held, would share block `host`'s launch on the current device.
+ * The hold serves the backward pass the same way: armed in front of an ms_conv_block_bwd_ex whose DATA GRADIENT runs the clip-resident
+ * kernel (ms_clip_dgrad_grid(d) > 0), it keeps that one launch back -- the call's other launches (BatchNorm backward, weight
+ * gradient) go as usual -- and the data gradient of the stream's next ms_conv_block_bwd_ex carries it under the same conditions
+ * (ms_clip_dgrad_pair_ok).  A forward block and a data gradient never share a launch.  (Twin entry points: no signature of ABI 4
+ * changed.) */
 int ms_clip_hold(void* stream);
 int ms_clip_hold_flush(void* stream);
 int ms_clip_hold_discard(void* stream);
 int ms_clip_grid(const ms_conv_desc* d);
 int ms_clip_pair_ok(const ms_conv_desc* host, const ms_conv_desc* guest);
+int ms_clip_dgrad_grid(const ms_conv_desc* d);
+int ms_clip_dgrad_pair_ok(const ms_conv_desc* host, const ms_conv_desc* guest);
 /* bf16x6 mode (ms_set_precision): bytes of the block's split weight planes (0: the block runs the fp32 kernels), and their
  * batched construction for n blocks in one launch -- once per optimizer update, like ms_dgrad_weights_prepare. */
 size_t ms_fwd_weights_bytes(const ms_conv_desc* d);

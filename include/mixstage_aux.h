@@ -75,6 +75,8 @@ int ms_debug_set_clip32(int on);
 /* A/B runs: 0 = a held forward block (ms_clip_hold) never shares a launch, it is launched on its own in front of the next block
  * (also MS_CLIP_CORUN=0 in the environment); returns the previous value. */
 int ms_debug_set_clip_corun(int on);
+/* ... 0 = only a held DATA GRADIENT never shares a launch (also MS_CLIP_CORUN_BWD=0); forward blocks are not affected. */
+int ms_debug_set_clip_corun_bwd(int on);
 
 /* Self-test kernel: C(32x32) = A(32xK) * B(Kx32) through the fp32 MFMA path (checks fragment maps). */
 int ms_selftest_mfma(const float* A, const float* B, float* C, int K, void* stream);

@@ -177,6 +177,9 @@ SIGNATURES = {
     'ms_clip_hold_discard': (c_int, [_P]),
     'ms_clip_grid': (c_int, [_DESC]),
     'ms_clip_pair_ok': (c_int, [_DESC, _DESC]),
+    'ms_clip_dgrad_grid': (c_int, [_DESC]),
+    'ms_clip_dgrad_pair_ok': (c_int, [_DESC, _DESC]),
+    'ms_debug_set_clip_corun_bwd': (c_int, [c_int]),
     'ms_debug_set_wgrad16_target': (c_int, [c_int]),
     'ms_debug_set_wgrad16_ring': (c_int, [c_int]),
     'ms_debug_set_wgrad_target': (c_int, [c_int]),

@@ -190,9 +190,9 @@ int ms_conv_block_fwd_ex(const ms_conv_desc* d, const float* x, const float* x2,
                          const ms_fwd_options* opt) {
   // the stream's hold (ms_clip_hold): a block held back from an earlier call goes first unless this call can share its launch
   const bool clip_path = d && dt_of(d) == DT_F32 && g_precision == 0 && !validate(d, "ms_conv_block_fwd") && clip32_fwd_ok(d);
-  int rc = clip32_fwd_call_begin((hipStream_t)stream, clip_path, workspace, workspace_bytes);
+  int rc = clip32_call_begin((hipStream_t)stream, clip_path, workspace, workspace_bytes);
   if (!rc) rc = conv_block_fwd_impl(d, x, x2, w, bias, gamma, beta, running_mean, running_var, y_raw, y, save, workspace, workspace_bytes, stream, opt);
-  clip32_fwd_call_end((hipStream_t)stream);
+  clip32_call_end((hipStream_t)stream);
   return rc;
 }
 
@@ -508,19 +508,42 @@ int ms_conv_block_bwd_overlap(const ms_conv_desc* d, const float* x, const float
                               dgamma, dbeta, workspace, workspace_bytes, stream, &o);
 }
 
+static int conv_block_bwd_impl(const ms_conv_desc* d, const float* x, const float* x2, const float* w, const float* gamma,
+                               const float* running_mean, const float* running_var, const float* y_raw, const float* y,
+                               const float* save, const float* dy, float* dyr, float* dx, float* dx2, float* dw, float* dbias,
+                               float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream,
+                               const ms_bwd_options* opt);
+
 int ms_conv_block_bwd_ex(const ms_conv_desc* d, const float* x, const float* x2, const float* w, const float* gamma,
                          const float* running_mean, const float* running_var, const float* y_raw, const float* y,
                          const float* save, const float* dy, float* dyr, float* dx, float* dx2, float* dw, float* dbias,
                          float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream,
                          const ms_bwd_options* opt) {
+  // the stream's hold (ms_clip_hold), as in ms_conv_block_fwd_ex: a data gradient held back from an earlier call goes first unless
+  // this call's data gradient can share its launch
+  int rc = validate(d, "ms_conv_block_bwd");      // (once, here: a bad descriptor leaves the hold as it is)
+  if (rc) return rc;
+  const bool side = opt && opt->side_stream && opt->side_stream != stream;
+  const bool clip_path = dx && !side && dt_of(d) == DT_F32 && g_precision == 0 && clip32_dgrad_ok(d);
+  rc = clip32_call_begin((hipStream_t)stream, clip_path, workspace, workspace_bytes);
+  if (!rc) rc = conv_block_bwd_impl(d, x, x2, w, gamma, running_mean, running_var, y_raw, y, save, dy, dyr, dx, dx2, dw, dbias, dgamma, dbeta,
+                                    workspace, workspace_bytes, stream, opt);
+  clip32_call_end((hipStream_t)stream);
+  return rc;
+}
+
+static int conv_block_bwd_impl(const ms_conv_desc* d, const float* x, const float* x2, const float* w, const float* gamma,
+                               const float* running_mean, const float* running_var, const float* y_raw, const float* y,
+                               const float* save, const float* dy, float* dyr, float* dx, float* dx2, float* dw, float* dbias,
+                               float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream,
+                               const ms_bwd_options* opt) {
   (void)running_mean; (void)running_var;
   ms_bwd_options none = {};
   if (!opt) opt = &none;
   void* side_stream = opt->side_stream;
   const float* wt_prepared = opt->wt_prepared;
   const bool defer_wgrad = opt->wgrad_partials != nullptr;
-  int rc = validate(d, "ms_conv_block_bwd");
-  if (rc) return rc;
+  int rc = 0;                                      // (d is validated: ms_conv_block_bwd_ex)
   if (d->mode == MS_BN_EVAL) return set_error("ms_conv_block_bwd: BN_EVAL blocks are never differentiated on the path");
   if (!dy || !w || !workspace) return set_error("ms_conv_block_bwd: null tensor");
   if (d->mode == MS_BN_TRAIN && !opt->dy_is_dyr && (!y_raw || !save || !gamma || !dyr)) return set_error("ms_conv_block_bwd: BN_TRAIN needs y_raw/save/gamma/dyr");
@@ -614,7 +637,8 @@ int ms_conv_block_bwd_ex(const ms_conv_desc* d, const float* x, const float* x2,
     // (the data-gradient paths below know nothing of dx_accum: a decline must not leave dx without it)
     if (rc == -2 && opt->dx_accum) return set_error("ms_conv_block_bwd: the clip-resident data gradient declined a launch with dx_accum");
     dx_done = rc == 0;
-    rc = 0;
+    rc = dx_done ? 0 : clip32_hold_flush(s);      // (a decline: in stream order behind a block the stream's hold may still hold)
+    if (rc) return rc;
   }
   if (dx && !dx_done && p.dg_grouped) {
     // grouped decoder blocks: one clip of one group per workgroup, all 256 rows, weights streamed into registers (chain32.hip)
@@ -767,9 +791,22 @@ int ms_clip_pair_ok(const ms_conv_desc* host, const ms_conv_desc* guest) {
   if (validate(host, "ms_clip_pair_ok") || validate(guest, "ms_clip_pair_ok") || dt_of(host) != DT_F32 || dt_of(guest) != DT_F32 || g_precision != 0) return 0;
   return clip32_fwd_pair_ok(host, guest) ? 1 : 0;
 }
+int ms_clip_dgrad_grid(const ms_conv_desc* d) {
+  if (validate(d, "ms_clip_dgrad_grid") || dt_of(d) != DT_F32 || g_precision != 0) return 0;
+  return clip32_dgrad_grid(d);
+}
+int ms_clip_dgrad_pair_ok(const ms_conv_desc* host, const ms_conv_desc* guest) {
+  if (validate(host, "ms_clip_dgrad_pair_ok") || validate(guest, "ms_clip_dgrad_pair_ok") || dt_of(host) != DT_F32 || dt_of(guest) != DT_F32 || g_precision != 0) return 0;
+  return clip32_dgrad_pair_ok(host, guest) ? 1 : 0;
+}
 int ms_debug_set_clip_corun(int on) {
   const int prev = g_clip_corun < 0 ? 1 : g_clip_corun;
   g_clip_corun = on ? 1 : 0;
+  return prev;
+}
+int ms_debug_set_clip_corun_bwd(int on) {
+  const int prev = g_clip_corun_bwd < 0 ? 1 : g_clip_corun_bwd;
+  g_clip_corun_bwd = on ? 1 : 0;
   return prev;
 }
 

@@ -642,22 +642,22 @@ __global__ __launch_bounds__(256, 1) void clip32_kernel(const Clip32Args p) {
   clip32_body<KW, S, NB, UP2, K8W, DG2>(p, blockIdx.x);
 }
 
-// Two independent forward blocks in ONE launch on disjoint compute units: workgroups [0, nA) are block A's grid, [nA, nA + nB)
-// block B's (with nA % 8 == 0, so that B's workgroups land on the XCDs they would in a launch of their own).  Each block keeps its
-// own partials, meeting counters and sync words; the dynamic LDS is the larger of the two images.
+// Two independent blocks -- two forward blocks, or two data gradients -- in ONE launch on disjoint compute units: workgroups [0, nA)
+// are block A's grid, [nA, nA + nB) block B's (with nA % 8 == 0, so that B's workgroups land on the XCDs they would in a launch of
+// their own).  Each block keeps its own partials, meeting counters and sync words; the dynamic LDS is the larger of the two images.
 struct ClipPairArgs {
   int nA;
   Clip32Args a, b;
 };
-template <int KWA, int SA, int NBA, bool UP2A, int K8WA, int KWB, int SB, int NBB, bool UP2B, int K8WB>
+template <int KWA, int SA, int NBA, bool UP2A, int K8WA, int KWB, int SB, int NBB, bool UP2B, int K8WB, bool DG2A = false, bool DG2B = false>
 __global__ __launch_bounds__(256, 1) void clip32_pair_kernel(const ClipPairArgs pp) {
   const unsigned bid = blockIdx.x;
   if (bid < (unsigned)pp.nA) {
     prefetch_kernargs<sizeof(Clip32Args)>();
-    clip32_body<KWA, SA, NBA, UP2A, K8WA>(pp.a, bid);
+    clip32_body<KWA, SA, NBA, UP2A, K8WA, DG2A>(pp.a, bid);
   } else {
     prefetch_kernargs<384>((int)offsetof(ClipPairArgs, b));
-    clip32_body<KWB, SB, NBB, UP2B, K8WB>(pp.b, bid - (unsigned)pp.nA);
+    clip32_body<KWB, SB, NBB, UP2B, K8WB, DG2B>(pp.b, bid - (unsigned)pp.nA);
   }
 }
 
@@ -833,29 +833,53 @@ struct ClipJob {
   Clip32Args a;
   int KW, S, nb, nwg, lds;
   bool up2, dg2;
+  bool bwd;              // a data gradient (clip32_block_dgrad)
   const char* what;
   double flops, bytes;
 };
 
-// ---- the pair instances: (host, guest) of the headline path -- a UNet1D block beside a PoseStyleEncoder block.  Anything else is
-// "not mergeable": the two blocks get a launch each.
+// ---- the pair instances: (host, guest) of the headline path -- a UNet1D block beside a PoseStyleEncoder block, forward beside
+// forward and data gradient beside data gradient.  Anything else is "not mergeable": the two blocks get a launch each.
 enum { CLIP_HOST_DOWN8 = 0, CLIP_HOST_UP8 = 1, CLIP_HOSTS = 2 };                     // <4,2,1,false,8>, <3,1,2,true,8>
 enum { CLIP_GUEST_K3_4 = 0, CLIP_GUEST_DOWN2 = 1, CLIP_GUEST_DOWN4 = 2, CLIP_GUEST_DOWN8 = 3, CLIP_GUESTS = 4 };
+// data gradients.  Hosts: the UNet's up path <3,1,2,false,8,false> (transposed k3 s1; EP_DGRAD_UP2 at run time) and its down path
+// <4,1,2,false,8,true> (DG2).  Guests: the style encoder's k4 s2 blocks <4,1,2,false,K8W,true>; K8W = 0 is its last block
+// (256 -> num_speakers: one channel group per wave, the run-time form)
+enum { CLIP_BHOST_UP8 = 0, CLIP_BHOST_DOWN8 = 1 };
+enum { CLIP_BGUEST_DG0 = 0, CLIP_BGUEST_DG2 = 1, CLIP_BGUEST_DG4 = 2, CLIP_BGUEST_DG8 = 3 };
 static int clip_host_kind(const ClipJob& j) {
-  if (j.dg2 || j.a.k8w != 8) return -1;
+  if (j.a.k8w != 8) return -1;
+  if (j.bwd) {
+    if (j.up2) return -1;
+    return j.dg2 ? CLIP_BHOST_DOWN8 : (j.KW == 3 && j.S == 1) ? CLIP_BHOST_UP8 : -1;
+  }
+  if (j.dg2) return -1;
   if (j.KW == 4 && j.S == 2 && !j.up2) return CLIP_HOST_DOWN8;
   if (j.KW == 3 && j.S == 1 && j.up2) return CLIP_HOST_UP8;
   return -1;
 }
 static int clip_guest_kind(const ClipJob& j) {
-  if (j.dg2 || j.up2) return -1;
+  if (j.up2) return -1;
+  if (j.bwd) {
+    if (!j.dg2) return -1;
+    return j.a.k8w == 2 ? CLIP_BGUEST_DG2 : j.a.k8w == 4 ? CLIP_BGUEST_DG4 : j.a.k8w == 8 ? CLIP_BGUEST_DG8 : j.a.k8w == 9 ? -1 : CLIP_BGUEST_DG0;
+  }
+  if (j.dg2) return -1;
   if (j.KW == 3 && j.S == 1) return j.a.k8w == 4 ? CLIP_GUEST_K3_4 : -1;
   if (j.KW == 4 && j.S == 2) return j.a.k8w == 2 ? CLIP_GUEST_DOWN2 : j.a.k8w == 4 ? CLIP_GUEST_DOWN4 : j.a.k8w == 8 ? CLIP_GUEST_DOWN8 : -1;
   return -1;
 }
-template <int KWA, int SA, int NBA, bool UP2A, int K8WA, int KWB, int SB, int NBB, bool UP2B, int K8WB>
+// the pairs with an instance: forward, every host with every guest; data gradients, the pairs a G-step of the headline shape
+// launches (up path beside the encoder's last two blocks, down path beside the others)
+static bool clip_pair_instance(const ClipJob& A, const ClipJob& B) {
+  const int h = clip_host_kind(A), g = clip_guest_kind(B);
+  if (h < 0 || g < 0 || A.bwd != B.bwd) return false;
+  if (!A.bwd) return true;
+  return h == CLIP_BHOST_UP8 ? (g == CLIP_BGUEST_DG0 || g == CLIP_BGUEST_DG8) : g != CLIP_BGUEST_DG0;
+}
+template <int KWA, int SA, int NBA, bool UP2A, int K8WA, int KWB, int SB, int NBB, bool UP2B, int K8WB, bool DG2A = false, bool DG2B = false>
 static int clip32_pair_launch_k(const ClipPairArgs& pp, int nwg, int lds_bytes, hipStream_t s) {
-  auto fn = clip32_pair_kernel<KWA, SA, NBA, UP2A, K8WA, KWB, SB, NBB, UP2B, K8WB>;
+  auto fn = clip32_pair_kernel<KWA, SA, NBA, UP2A, K8WA, KWB, SB, NBB, UP2B, K8WB, DG2A, DG2B>;
   static unsigned long long attr_done = 0;          // (per device)
   if (first_time_on_device(attr_done)) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
@@ -872,6 +896,18 @@ static int clip32_pair_launch_g(int guest, const ClipPairArgs& pp, int nwg, int 
     case CLIP_GUEST_DOWN2: return clip32_pair_launch_k<KWA, SA, NBA, UP2A, 8, 4, 2, 1, false, 2>(pp, nwg, lds_bytes, s);
     case CLIP_GUEST_DOWN4: return clip32_pair_launch_k<KWA, SA, NBA, UP2A, 8, 4, 2, 1, false, 4>(pp, nwg, lds_bytes, s);
     default: return clip32_pair_launch_k<KWA, SA, NBA, UP2A, 8, 4, 2, 1, false, 8>(pp, nwg, lds_bytes, s);
+  }
+}
+// data gradients (clip_pair_instance): the guest is always the DG2 form
+static int clip32_pair_launch_bwd(int host, int guest, const ClipPairArgs& pp, int nwg, int lds_bytes, hipStream_t s) {
+  if (host == CLIP_BHOST_UP8) {
+    if (guest == CLIP_BGUEST_DG0) return clip32_pair_launch_k<3, 1, 2, false, 8, 4, 1, 2, false, 0, false, true>(pp, nwg, lds_bytes, s);
+    return clip32_pair_launch_k<3, 1, 2, false, 8, 4, 1, 2, false, 8, false, true>(pp, nwg, lds_bytes, s);
+  }
+  switch (guest) {
+    case CLIP_BGUEST_DG2: return clip32_pair_launch_k<4, 1, 2, false, 8, 4, 1, 2, false, 2, true, true>(pp, nwg, lds_bytes, s);
+    case CLIP_BGUEST_DG4: return clip32_pair_launch_k<4, 1, 2, false, 8, 4, 1, 2, false, 4, true, true>(pp, nwg, lds_bytes, s);
+    default: return clip32_pair_launch_k<4, 1, 2, false, 8, 4, 1, 2, false, 8, true, true>(pp, nwg, lds_bytes, s);
   }
 }
 
@@ -914,10 +950,11 @@ static int clip32_issue(ClipJob& j, hipStream_t s) {
   return rc;
 }
 
-// ---- the one-slot hold of a stream (ms_clip_hold): a forward block planned but not yet launched, waiting for the next forward
-// block of the stream to share its launch with.  IDLE -> ARMED (ms_clip_hold) -> PENDING (a clip-path ms_conv_block_fwd_ex recorded
-// its job) -> IDLE (merged, launched alone, or discarded).
+// ---- the one-slot hold of a stream (ms_clip_hold): a block -- forward, or a data gradient -- planned but not yet launched, waiting
+// for the next block of the stream to share its launch with.  IDLE -> ARMED (ms_clip_hold) -> PENDING (a clip-path
+// ms_conv_block_fwd_ex / ms_conv_block_bwd_ex recorded its job) -> IDLE (merged, launched alone, or discarded).
 int g_clip_corun = -1;     // ms_debug_set_clip_corun / MS_CLIP_CORUN=0: never merge (A/B runs)
+int g_clip_corun_bwd = -1; // ms_debug_set_clip_corun_bwd / MS_CLIP_CORUN_BWD=0: never merge two data gradients
 enum { HOLD_IDLE = 0, HOLD_ARMED = 1, HOLD_PENDING = 2 };
 struct ClipHold {
   int state = HOLD_IDLE;
@@ -927,13 +964,17 @@ struct ClipHold {
 };
 static std::mutex g_hold_mu;
 static std::map<hipStream_t, ClipHold> g_hold;
-static thread_local bool t_in_fwd = false;            // inside ms_conv_block_fwd_ex (clip32_fwd_call_begin / _end)
+static thread_local bool t_in_call = false;            // inside ms_conv_block_fwd_ex / _bwd_ex (clip32_call_begin / _end)
 static thread_local const char* t_ws_lo = nullptr;
 static thread_local const char* t_ws_hi = nullptr;
 
 static bool clip_corun_on() {
   if (g_clip_corun < 0) { const char* e = getenv("MS_CLIP_CORUN"); g_clip_corun = e ? (atoi(e) != 0) : 1; }
   return g_clip_corun != 0;
+}
+static bool clip_corun_bwd_on() {
+  if (g_clip_corun_bwd < 0) { const char* e = getenv("MS_CLIP_CORUN_BWD"); g_clip_corun_bwd = e ? (atoi(e) != 0) : 1; }
+  return g_clip_corun_bwd != 0;
 }
 
 int clip32_hold_arm(hipStream_t s) {
@@ -961,11 +1002,11 @@ int clip32_hold_flush(hipStream_t s) {
   }
   return clip32_issue(job, s);
 }
-// ms_conv_block_fwd_ex brackets its work with these two.  begin: a pending block whose scratch this call shares, or a call that will
+// ms_conv_block_fwd_ex and ms_conv_block_bwd_ex bracket their work with these two.  begin: a pending block whose scratch this call shares, or a call that will
 // not take the clip path, sends the pending block off first (a clip path that declines at run time, -2, does so itself:
 // clip32_hold_flush).  end: a hold that this call did not use is disarmed.
-int clip32_fwd_call_begin(hipStream_t s, bool clip_path, const void* ws, size_t ws_bytes) {
-  t_in_fwd = true;
+int clip32_call_begin(hipStream_t s, bool clip_path, const void* ws, size_t ws_bytes) {
+  t_in_call = true;
   t_ws_lo = (const char*)ws; t_ws_hi = t_ws_lo + (ws ? ws_bytes : 0);
   bool flush = false;
   {
@@ -976,8 +1017,8 @@ int clip32_fwd_call_begin(hipStream_t s, bool clip_path, const void* ws, size_t 
   }
   return flush ? clip32_hold_flush(s) : 0;
 }
-void clip32_fwd_call_end(hipStream_t s) {
-  t_in_fwd = false;
+void clip32_call_end(hipStream_t s) {
+  t_in_call = false;
   std::lock_guard<std::mutex> lk(g_hold_mu);
   auto it = g_hold.find(s);
   if (it != g_hold.end() && it->second.state == HOLD_ARMED) it->second.state = HOLD_IDLE;      // the call took another path
@@ -987,8 +1028,8 @@ void clip32_fwd_call_end(hipStream_t s) {
 // the merged grid is resident at once -- the condition under which either block's workgroups may wait for one another --, and the
 // two blocks share neither partials nor counters.
 static bool clip_pair_fits(const ClipJob& A, const ClipJob& B) {
-  if (!clip_corun_on()) return false;
-  if (clip_host_kind(A) < 0 || clip_guest_kind(B) < 0) return false;
+  if (!clip_corun_on() || (A.bwd && !clip_corun_bwd_on())) return false;
+  if (!clip_pair_instance(A, B)) return false;
   if (A.nwg % 8) return false;
   int cus = current_device_cus();
   if (cus <= 0) cus = 256;
@@ -996,7 +1037,8 @@ static bool clip_pair_fits(const ClipJob& A, const ClipJob& B) {
 }
 static bool clip_pair_ok(const ClipJob& A, const ClipJob& B) {
   if (!clip_pair_fits(A, B)) return false;
-  const bool meetA = A.a.ep == EP_RAW_STATS && A.a.npw > 1, meetB = B.a.ep == EP_RAW_STATS && B.a.npw > 1;
+  auto meets = [](const ClipJob& j) { return (j.a.ep == EP_RAW_STATS || j.a.ep == EP_DGRAD_BN) && j.a.npw > 1; };
+  const bool meetA = meets(A), meetB = meets(B);
   if (meetA && meetB && (A.a.part == B.a.part || A.a.sync == B.a.sync)) return false;
   return true;
 }
@@ -1011,13 +1053,15 @@ static int clip32_issue_pair(ClipJob& A, ClipJob& B, hipStream_t s) {
   pp.nA = A.nwg; pp.a = A.a; pp.b = B.a;
   pp.a.stamps = pp.b.stamps = nullptr;
   const int nwg = A.nwg + B.nwg, lds = std::max(A.lds, B.lds), guest = clip_guest_kind(B);
+  if (A.bwd) return clip32_pair_launch_bwd(clip_host_kind(A), guest, pp, nwg, lds, s);
   return clip_host_kind(A) == CLIP_HOST_DOWN8 ? clip32_pair_launch_g<4, 2, 1, false>(guest, pp, nwg, lds, s)
                                               : clip32_pair_launch_g<3, 1, 2, true>(guest, pp, nwg, lds, s);
 }
 
 // ep: EP_BARE / EP_LRELU / EP_BN_EVAL / EP_RAW_STATS (= BN_TRAIN, everything in this launch) / EP_DGRAD_UP2
 // plan_only: fills *plan and launches nothing (ms_clip_grid)
-int clip32_launch(Clip32Args a, int KW, int S, bool up2, const char* what, hipStream_t s, bool dg2 = false, ClipJob* plan = nullptr) {
+int clip32_launch(Clip32Args a, int KW, int S, bool up2, const char* what, hipStream_t s, bool dg2 = false, ClipJob* plan = nullptr,
+                  bool bwd = false) {
   const int nb = (S == 2 && !dg2) ? 1 : 2, npx = 32 * nb;
   a.k8w = clip_k8w(a.Cin);
   a.npw = a.B * a.To / npx;
@@ -1054,12 +1098,12 @@ int clip32_launch(Clip32Args a, int KW, int S, bool up2, const char* what, hipSt
   // register file of the upsample-add instance does not)
   if ((a.ep == EP_RAW_STATS || a.ep == EP_DGRAD_BN) && a.npw > 1 && nwg > cus) return -2;      // caller falls back to the per-layer kernels
   ClipJob job;
-  job.a = a; job.KW = KW; job.S = S; job.nb = nb; job.nwg = nwg; job.lds = lds; job.up2 = up2; job.dg2 = dg2; job.what = what;
+  job.a = a; job.KW = KW; job.S = S; job.nb = nb; job.nwg = nwg; job.lds = lds; job.up2 = up2; job.dg2 = dg2; job.bwd = bwd; job.what = what;
   job.flops = 2.0 * a.rows_valid * a.Cin * (dg2 ? 2 : KW) * (double)a.B * a.To;
   job.bytes = 4.0 * ((double)a.rows_valid * a.Cin * KW + (double)a.B * a.Cin * a.Ti + (double)a.B * a.rows_valid * a.To);
   if (plan) { *plan = job; return 0; }
-  if (t_in_fwd) {
-    // a forward block inside ms_conv_block_fwd_ex: the stream's hold takes it (ARMED), or hands over the block it holds (PENDING)
+  if (t_in_call) {
+    // a block inside ms_conv_block_fwd_ex / _bwd_ex: the stream's hold takes it (ARMED), or hands over the block it holds (PENDING)
     ClipJob held;
     int st;
     {
@@ -1153,9 +1197,29 @@ int clip32_block_dgrad(const ms_conv_desc* d, const float* g, const float* wp, f
   }
   if (d->KW == 4) {                                  // k4 s2 block: the image is dy_raw at half the output's resolution
     a.Ti = d->OW;
-    return clip32_launch(a, 4, 2, false, "dgrad", s, true);
+    return clip32_launch(a, 4, 2, false, "dgrad", s, true, nullptr, true);
   }
-  return clip32_launch(a, 3, 1, false, "dgrad", s);
+  return clip32_launch(a, 3, 1, false, "dgrad", s, false, nullptr, true);
+}
+
+// the workgroups of block d's data-gradient launch on the clip path, 0 where it does not run there
+static int clip32_dgrad_plan(const ms_conv_desc* d, ClipJob* plan) {
+  if (!clip32_dgrad_ok(d)) return 0;
+  Clip32Args a = {};
+  a.B = d->B; a.Cin = d->Cout; a.Cout = d->Cin; a.rows_valid = d->Cin; a.To = d->W; a.Ti = d->KW == 4 ? d->OW : d->W;
+  a.ep = d->in_mode == MS_IN_UP2ADD ? EP_DGRAD_UP2 : EP_BARE;
+  plan->nwg = 0;
+  if (clip32_launch(a, d->KW == 4 ? 4 : 3, d->KW == 4 ? 2 : 1, false, "dgrad", nullptr, d->KW == 4, plan, true) != 0) return 0;
+  return plan->nwg;
+}
+int clip32_dgrad_grid(const ms_conv_desc* d) {
+  ClipJob plan;
+  return clip32_dgrad_plan(d, &plan);
+}
+// would the data gradient of block `guest`, held, share the launch of block `host`'s (given separate scratch and counters)?
+bool clip32_dgrad_pair_ok(const ms_conv_desc* host, const ms_conv_desc* guest) {
+  ClipJob A, B;
+  return clip32_dgrad_plan(host, &A) > 0 && clip32_dgrad_plan(guest, &B) > 0 && clip_pair_fits(A, B);
 }
 
 }  // namespace ms

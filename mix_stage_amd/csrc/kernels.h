@@ -187,13 +187,17 @@ int clip32_block_fwd(const ms_conv_desc* d, const float* x, const float* x2, con
                      const float* beta, float* rm, float* rv, float* y_raw, float* y, float* save, float* part, int* sync,
                      int sync_words, hipStream_t s);
 // One-slot hold per stream (ms_clip_hold): a forward block on the clip path is planned but not launched, and shares the launch of the
-// stream's next forward block when the two have a pair instance and fit the device together (clip32.hip: clip32_pair_kernel)
+// stream's next forward block when the two have a pair instance and fit the device together (clip32.hip: clip32_pair_kernel).  The
+// same for two data gradients (ms_conv_block_bwd_ex brackets its work with the same begin / end).
 extern int g_clip_corun;
+extern int g_clip_corun_bwd;
+int clip32_dgrad_grid(const ms_conv_desc* d);
+bool clip32_dgrad_pair_ok(const ms_conv_desc* host, const ms_conv_desc* guest);
 int clip32_hold_arm(hipStream_t s);
 int clip32_hold_flush(hipStream_t s);
 void clip32_hold_discard(hipStream_t s);
-int clip32_fwd_call_begin(hipStream_t s, bool clip_path, const void* ws, size_t ws_bytes);
-void clip32_fwd_call_end(hipStream_t s);
+int clip32_call_begin(hipStream_t s, bool clip_path, const void* ws, size_t ws_bytes);
+void clip32_call_end(hipStream_t s);
 int clip32_fwd_grid(const ms_conv_desc* d);
 bool clip32_fwd_pair_ok(const ms_conv_desc* host, const ms_conv_desc* guest);
 // BatchNorm + LeakyReLU backward of the block that PRODUCED the input of block d (its output y / y_raw, save, gamma; gradient slots),

@@ -55,7 +55,10 @@ def _ensure_counters(device):
 
 
 
-_corun = {'driver': None, 'held': False, 'keep': [], 'on': os.environ.get('MS_CLIP_CORUN', '1') != '0', 'merges_offered': 0}
+_corun = {'driver': None, 'held': False, 'keep': [], 'on': os.environ.get('MS_CLIP_CORUN', '1') != '0', 'merges_offered': 0,
+          # the backward twin (_ConvBlockFn.backward): 'in_guest' while a guest chain's forward block runs, 'bwd_keep' what a held
+          # data gradient touches, 'bwd_offered' data gradients held back for the next block's launch
+          'in_guest': False, 'bwd_on': os.environ.get('MS_CLIP_CORUN_BWD', '1') != '0', 'bwd_keep': [], 'bwd_offered': 0}
 
 
 def workspace(nbytes, device):
@@ -232,6 +235,9 @@ def reset_deferred_wgrad():
   _deferred['jobs'].clear()
   _deferred['keep'].clear()
   _deferred['queued'] = False
+  if _corun['bwd_keep']:
+    lib().ms_clip_hold_discard(_stream())
+    _corun['bwd_keep'].clear()
   if _deferred['launches']:
     _deferred['launches'] = 0
     lib().ms_wgrad_discard()
@@ -276,6 +282,8 @@ def _wgrad_partials_for(w, d):
 def _flush_deferred_wgrad():
   jobs = _deferred['jobs']
   _deferred['queued'] = False
+  if _corun['bwd_keep']:
+    _bwd_hold_release()           # (a data gradient still held goes in front of the queued weight gradients)
   if _deferred['launches']:
     _deferred['launches'] = 0
     try:
@@ -421,6 +429,7 @@ class _ConvBlockFn(torch.autograd.Function):
   def forward(ctx, x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, pre=None, prev=None, link=None):
     rm, rv = stats if stats is not None else (None, None)
     _need_hip(x, x2, w, bias, gamma, beta, rm, rv)
+    xin = x                              # (the caller's tensor: its grad_fn is the node that will read this block's dx)
     x = x.contiguous()
     x2 = x2.contiguous() if x2 is not None else None
     nd = geom.nd
@@ -471,6 +480,15 @@ class _ConvBlockFn(torch.autograd.Function):
         _corun['keep'].append((x, x2, w, bias, gamma, beta, rm, rv, y_raw, y, save, ws, planes, sync))
     ctx.geom_desc = d
     ctx.mode, ctx.in_mode = mode, in_mode
+    # a block of a guest chain (corun): its node was created between the host's nodes, so autograd runs its backward between the
+    # host's too, and its data gradient may wait for the next host block's launch (backward: _bwd_guest_ok).  Only where the
+    # reader of that data gradient is known to pass through the hold first: x is the output of another conv block of this
+    # class, whose backward flushes or takes a held launch before it reads anything, and nobody watches x (a tensor hook or
+    # retain_grad() would read the gradient as soon as this block's backward returns).  The chain's first block, whose input
+    # comes from a transpose, launches at once.
+    ctx.corun_guest = bool(_corun['in_guest'] and pre is None and nd == 1 and xin is not None and xin.grad_fn is not None
+                           and type(xin.grad_fn).__name__ == '_ConvBlockFnBackward'
+                           and not (getattr(xin, '_backward_hooks', None) or getattr(xin, 'retains_grad', False)))
     # `prev`: the autograd node of the BN_TRAIN block that produced x, handed over by a container that knows x has no other
     # consumer (layers.py: the 1-D stacks).  If this block's data-gradient launch can carry that block's BatchNorm + LeakyReLU
     # backward (ms_bwd_options.prev_*), the backward pass fuses the two: one launch and one pass over dy fewer per block.
@@ -505,6 +523,18 @@ class _ConvBlockFn(torch.autograd.Function):
 
   @staticmethod
   def backward(ctx, dy):
+    try:
+      return _ConvBlockFn._backward(ctx, dy)
+    except BaseException:
+      if _corun['held'] or _corun['bwd_keep']:
+        lib().ms_clip_hold_discard(_stream())      # (a held data gradient is dropped with the failed pass)
+        _corun['bwd_keep'].clear()
+      raise
+    finally:
+      _corun['held'] = False
+
+  @staticmethod
+  def _backward(ctx, dy):
     x, x2, w, gamma, y_raw, y, save = ctx.saved_tensors
     d, mode, in_mode = ctx.geom_desc, ctx.mode, ctx.in_mode
     if mode == MS_BN_EVAL:
@@ -558,8 +588,17 @@ class _ConvBlockFn(torch.autograd.Function):
         raise RuntimeError('residual link: a residual gradient of shape %s arrived for an input of shape %s (needs grad: %s)' %
                            (tuple(acc.shape), tuple(x.shape), want_dx))
     acc_in_launch = False
-    ws = workspace(d._bwd_ws, dev)
     side = _overlap['stream']
+    # ---- a guest chain's block (corun): its data gradient is planned now and launched with the next block's (ms_clip_hold) -- in
+    # the backward pass that next block is a host's, because the guest's node sits between the host's nodes
+    guest = bool(ctx.corun_guest and want_dx and side is None and _bwd_guest_ok(d, dy))
+    if guest and _corun['bwd_keep']:
+      _bwd_hold_release()                  # (a guest's data gradient that no host took goes in front of the next guest's)
+    if guest:
+      check(lib().ms_clip_hold(_stream()), 'ms_clip_hold')
+      _corun['held'] = True                # (scratch of its own until its launch is on the stream: workspace(); backward() resets it)
+      _corun['bwd_offered'] += 1
+    ws = workspace(d._bwd_ws, dev)
     if side is not None and need_w and direct_w is not True:
       # a second contribution to a parameter in this step (autograd will add it on this stream): the first one may
       # still be in flight on the side stream
@@ -615,6 +654,13 @@ class _ConvBlockFn(torch.autograd.Function):
                                       _ptr(y), _ptr(save), _ptr(dy), _ptr(dyr), _ptr(dx), _ptr(dx2), _ptr(dw),
                                       _ptr(dbias), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel(), _stream()),
               'ms_conv_block_bwd')
+    if guest:
+      # planned, not launched yet (ms_clip_hold): everything the launch touches stays allocated until it is on the stream -- with
+      # the next conv block's data gradient, or at the end of the backward pass
+      _corun['bwd_keep'].append((x, x2, w, gamma, y_raw, y, save, dy, dyr, dx, dx2, ws, wt, acc, fuse))
+      torch.autograd.Variable._execution_engine.queue_callback(_bwd_hold_end)     # (one per guest: the first to run does the work)
+    elif _corun['bwd_keep']:
+      _bwd_hold_release()                   # (this block's launch took the held one, or sent it off first)
     if acc is not None and not acc_in_launch:
       dx.add_(acc)                          # (side-stream experiment path: no options struct)
     if ctx.link is not None and ctx.link[1] == 'residual' and dx2 is not None and ctx.needs_input_grad[1] and not ctx.link[0].taken:
@@ -720,13 +766,13 @@ class _CoRun:
     self._resume()           # up to the first block (the chain's own preparation runs here)
 
   def _resume(self):
-    self.in_guest = True
+    self.in_guest = _corun['in_guest'] = True
     try:
       self.next_desc = next(self.gen)
     except StopIteration as e:
       self.done, self.result, self.next_desc = True, e.value, None
     finally:
-      self.in_guest = False
+      self.in_guest = _corun['in_guest'] = False
 
   def offer(self, x, x2, w, geom, mode, in_mode):
     """Called in front of a host block: True when the guest's next block is now held for this block's launch."""
@@ -790,6 +836,44 @@ def corun_ok(*tensors):
 def enable_corun(on):
   old = _corun['on']
   _corun['on'] = bool(on)
+  return old
+
+
+# The backward twin.  Nothing drives it: the guest chain's nodes were created between the host's nodes (the held guest block first,
+# then the host block that carried it), and autograd runs ready nodes latest-created first -- so the guest's backward blocks arrive
+# between the host's, each directly in front of a host block.  A guest block holds its data-gradient launch back (ms_clip_hold);
+# the next conv block's ms_conv_block_bwd_ex takes it into its own data-gradient launch or sends it off first, and whatever is
+# still held at the end of the backward pass goes in front of the queued weight gradients.  That order of the engine (ready nodes by
+# descending sequence number) is how PyTorch behaves, not a documented guarantee: only the GAIN depends on it
+# (tests/test_gpu_clip_corun_bwd.py: test_the_backward_corun_is_not_vacuous would show its loss).  The results do not: a block is a
+# guest only when the one reader of its data gradient is another conv block's backward (_ConvBlockFn.forward: corun_guest), and
+# every conv block's backward passes through the hold before it reads anything -- in any other order of the nodes the held
+# launch goes first, on its own, with the same bits.
+def _bwd_guest_ok(d, dy):
+  from . import ops16
+  return bool(_corun['on'] and _corun['bwd_on'] and _corun['driver'] is None and not bn_sync_active() and not _stat_pair['on']
+              and ops16.in_launch_meetings() and dy.is_cuda and dy.dtype == torch.float32 and lib().ms_get_precision() == 0
+              and lib().ms_clip_dgrad_grid(ctypes.byref(d)) > 0)
+
+
+def _bwd_hold_release():
+  """A data gradient still held goes now (nothing happens if a launch took it); what it touches is let go."""
+  try:
+    check(lib().ms_clip_hold_flush(_stream()), 'ms_clip_hold_flush')
+  finally:
+    _corun['bwd_keep'].clear()
+
+
+def _bwd_hold_end():
+  if _corun['bwd_keep']:
+    _bwd_hold_release()
+
+
+def enable_corun_bwd(on):
+  """MS_CLIP_CORUN_BWD: the style encoder's data gradients inside the UNet's data-gradient launches (A/B runs, tests)."""
+  old = _corun['bwd_on']
+  _corun['bwd_on'] = bool(on)
+  lib().ms_debug_set_clip_corun_bwd(1 if on else 0)
   return old
 
 
