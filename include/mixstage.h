@@ -646,6 +646,26 @@ int ms_adam_step_segmented_scaled_lr(float* p, const float* g, float* m, float* 
                                      const int32_t* seg_of_chunk, const int32_t* seg_first_step, float* seg_scratch, int n_seg,
                                      int32_t* loss_scale_state, int32_t growth_interval, float min_scale, float max_scale,
                                      const int32_t* const* meeting_words, int n_meeting_words, void* stream);
+/* The four above with an EXPONENTIAL MOVING AVERAGE of the weights kept inside the element pass, ONE entry point:
+ *   lr_dev != NULL            lr is read from the word (the _lr forms) and `lr` is ignored; NULL: `lr` by value
+ *   loss_scale_state != NULL  the scaled forms (norm is required and is un-scaled in place, the scale moves by their rule);
+ *                             NULL: unscaled, and growth_interval .. n_meeting_words are ignored
+ * `ema`: n fp32 values on the device with the layout of p, initialised by the caller (usually a copy of p).  For every element
+ * the pass updates, with p' the new weight:
+ *   t = p' - ema (rounded to fp32);  ema' = fma(om, t, ema),  om = 1.0f - ema_decay (exact for ema_decay >= 0.5)
+ * in the same launch that writes m, v and p': two launches as the other forms (the unchanged prep kernel of the form, then the
+ * pass), p, m, v, step_state, seg_scratch and norm bit-identical to the form without the average.  An element the pass leaves
+ * alone keeps its average: a refused step (step_state[2] = 1: non-finite norm, overflow skip, bad lr word), a segment that never
+ * had a gradient, a segment whose first step is still ahead.  The 16-byte path needs ema 16-byte aligned like p, g, m and v;
+ * otherwise the scalar path runs and gives the same bits.
+ * Refused (non-zero return, ms_last_error, nothing launched, nothing written): ema == NULL; ema_decay NaN, infinite, negative or
+ * >= 1; and, in the scaled form, what ms_adam_step_segmented_scaled refuses. */
+int ms_adam_step_segmented_ema(float* p, const float* g, float* m, float* v, size_t n, float* norm, float max_norm,
+                               float lr, const float* lr_dev, float beta1, float beta2, float eps, int32_t* step_state,
+                               const int32_t* seg_of_chunk, const int32_t* seg_first_step, float* seg_scratch, int n_seg,
+                               int32_t* loss_scale_state, int32_t growth_interval, float min_scale, float max_scale,
+                               const int32_t* const* meeting_words, int n_meeting_words, float* ema, float ema_decay,
+                               void* stream);
 size_t ms_reduce_partials_count(size_t n); /* floats needed in `partials` of ms_sqnorm / ms_l1_mean_fwd */
 
 #ifdef __cplusplus

@@ -162,6 +162,9 @@ SIGNATURES = {
                                           c_int, _P]),
     'ms_adam_step_segmented_scaled_lr': (c_int, [_P, _P, _P, _P, c_size_t, _P, c_float, _P, c_float, c_float, c_float, _P, _P, _P, _P,
                                                  c_int, _P, ctypes.c_int32, c_float, c_float, _P, c_int, _P]),
+    # (all four forms with the weights' moving average: lr AND lr_dev, the loss-scale block, then ema and its decay)
+    'ms_adam_step_segmented_ema': (c_int, [_P, _P, _P, _P, c_size_t, _P, c_float, c_float, _P, c_float, c_float, c_float, _P, _P, _P, _P,
+                                           c_int, _P, ctypes.c_int32, c_float, c_float, _P, c_int, _P, c_float, _P]),
     'ms_reduce_partials_count': (c_size_t, [c_size_t]),
     'ms_timing_enable': (c_int, [c_int]),
     'ms_timing_report': (c_size_t, [ctypes.c_char_p, c_size_t]),

@@ -76,7 +76,8 @@ def read_weights(source, trusted=False):
 def load_weights(model, source, strict=True, trusted=False):
   """Load reference-format weights into a mix_stage_amd GAN (or any sub-module).  Floating-point tensors are cast to the
   module's dtype (fp64 checkpoints -> fp32); parameters owned by a MixStageTrainStep keep living in its flat buffers (the copy
-  is in place) and the trainer notices the edit through the parameters' version counters."""
+  is in place) and the trainer notices the edit through the parameters' version counters.  A trainer's moving average of the
+  generator (MixStageTrainStep(ema_decay=)) is NOT touched: call train_step.optim_G.ema_reset() to restart it from these weights."""
   weights = read_weights(source, trusted=trusted)
   own = model.state_dict()
   cast = {}
@@ -90,13 +91,24 @@ def load_weights(model, source, strict=True, trusted=False):
   return model.load_state_dict(cast, strict=strict)
 
 
-def save_weights(model, path, train_step=None):
+def save_weights(model, path, train_step=None, ema=False):
   """Write `model.state_dict()` in the reference's container (a torch.save'd name -> CPU tensor mapping: what BookKeeper's
   `*_weights.p` holds, README.md:124-141).  With a MixStageTrainStep the device is checked first (check_health: a refused step or
-  an expired in-launch meeting raises there), and a state that holds a non-finite value is never written."""
+  an expired in-launch meeting raises there), and a state that holds a non-finite value is never written.
+  ema=True: the generator's PARAMETERS in the file are the trainer's moving average (MixStageTrainStep(ema_decay=)), everything
+  else -- the discriminator, every buffer -- is live; `model` is the trainer's GAN.  ValueError without such a trainer."""
+  if ema and (train_step is None or getattr(train_step, 'ema_decay', None) is None):
+    raise ValueError('save_weights(ema=True) needs train_step=, a MixStageTrainStep built with ema_decay')
+  if ema and model is not train_step.model:
+    raise ValueError("save_weights(ema=True): `model` must be the trainer's model (the average is its generator's)")
   if train_step is not None:
     train_step.check_health()
   state = {k: v.detach().to('cpu') for k, v in model.state_dict().items()}
+  if ema:
+    for k, v in train_step.ema_state_dict().items():
+      if 'G.' + k not in state:
+        raise KeyError('save_weights(ema=True): the model has no entry G.%s' % k)
+      state['G.' + k] = v.to('cpu')
   bad = [k for k, v in state.items() if v.is_floating_point() and not bool(torch.isfinite(v).all())]
   if bad:
     raise RuntimeError('refusing to save: %d tensors hold non-finite values (first: %s)' % (len(bad), bad[0]))

@@ -1341,11 +1341,16 @@ __global__ void adam_prep_seg_kernel(int32_t* state, const float* norm, float ma
   }
 }
 
+// The element pass is written once and instantiated twice: adam_seg_kernel<false> is the pass as it always was (`e` and `om` are
+// passed as NULL / 0 and never read: every statement that names them is compiled out), adam_seg_kernel<true> also moves an
+// exponential moving average of the weights: e' = fma(om, pn - e, e), om = 1 - decay, one more 16-byte load and store per lane
+// next to the seven of the pass.  An element the pass skips (refused step, inactive segment) keeps its `e`.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adam_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                        float* __restrict__ v, size_t n, const int32_t* __restrict__ state,
                                                        const int32_t* __restrict__ seg_of_chunk,
                                                        const float* __restrict__ seg_scratch, float beta1, float beta2,
-                                                       float eps) {
+                                                       float eps, float* __restrict__ e, float om) {
   const float coef = reinterpret_cast<const float*>(state)[1];
   if (state[2]) return;                        // non-finite gradient norm: no update (adam_prep_seg_kernel)
   // 16 bytes per lane and stream, two vectors per thread in flight (7 streams over the 60 MB of live parameters: dword accesses
@@ -1360,14 +1365,21 @@ __global__ __launch_bounds__(256) void adam_seg_kernel(float* __restrict__ p, co
     vn = fmaf(beta2, vo, gi * ((1.f - beta2) * gi));
     return fmaf(-step_size, mn / (sqrtf(vn) / bc2s + eps), pi);
   };
-  if ((n & 3) == 0 && ((((size_t)p | (size_t)g | (size_t)m | (size_t)v) & 15) == 0)) {
+  // the average: the difference is rounded, then one fma (contraction off, as above: both paths give the same bits)
+  auto avg = [&](float pn, float eo) {
+#pragma clang fp contract(off)
+    const float t = pn - eo;
+    return fmaf(om, t, eo);
+  };
+  if ((n & 3) == 0 && ((((size_t)p | (size_t)g | (size_t)m | (size_t)v | (EMA ? (size_t)e : (size_t)0)) & 15) == 0)) {
     const size_t n4 = n >> 2, stride = (size_t)gridDim.x * 256;
     float4* p4 = reinterpret_cast<float4*>(p);
     const float4* g4 = reinterpret_cast<const float4*>(g);
     float4* m4 = reinterpret_cast<float4*>(m);
     float4* v4 = reinterpret_cast<float4*>(v);
+    float4* e4 = reinterpret_cast<float4*>(e);
     for (size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x; i0 < n4; i0 += 2 * stride) {
-      float4 pv[2], gv[2], mv[2], vv[2];
+      float4 pv[2], gv[2], mv[2], vv[2], ev[2];
       float ss[2], bc[2];
       bool on[2];
 #pragma unroll
@@ -1377,7 +1389,10 @@ __global__ __launch_bounds__(256) void adam_seg_kernel(float* __restrict__ p, co
         const int sidx = seg_of_chunk[min(i, n4 - 1) >> 4];
         ss[u] = seg_scratch[2 * sidx]; bc[u] = seg_scratch[2 * sidx + 1];
         on[u] = on[u] && bc[u] != 0.f;         // never received a gradient: torch.optim.Adam skips it
-        if (on[u]) { pv[u] = p4[i]; gv[u] = g4[i]; mv[u] = m4[i]; vv[u] = v4[i]; }
+        if (on[u]) {
+          pv[u] = p4[i]; gv[u] = g4[i]; mv[u] = m4[i]; vv[u] = v4[i];
+          if constexpr (EMA) ev[u] = e4[i];
+        }
       }
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
@@ -1389,6 +1404,11 @@ __global__ __launch_bounds__(256) void adam_seg_kernel(float* __restrict__ p, co
         pn.z = upd(pv[u].z, gv[u].z, mv[u].z, vv[u].z, ss[u], bc[u], mn.z, vn.z);
         pn.w = upd(pv[u].w, gv[u].w, mv[u].w, vv[u].w, ss[u], bc[u], mn.w, vn.w);
         m4[i] = mn; v4[i] = vn; p4[i] = pn;
+        if constexpr (EMA) {
+          float4 en;
+          en.x = avg(pn.x, ev[u].x); en.y = avg(pn.y, ev[u].y); en.z = avg(pn.z, ev[u].z); en.w = avg(pn.w, ev[u].w);
+          e4[i] = en;
+        }
       }
     }
     return;
@@ -1402,6 +1422,7 @@ __global__ __launch_bounds__(256) void adam_seg_kernel(float* __restrict__ p, co
     m[i] = mn;
     v[i] = vn;
     p[i] = pn;
+    if constexpr (EMA) e[i] = avg(pn, e[i]);
   }
 }
 
@@ -1557,9 +1578,27 @@ int launch_adam_seg(float* p, const float* g, float* m, float* v, size_t n, cons
                     const float* seg_scratch, float beta1, float beta2, float eps, hipStream_t s) {
   int blocks = (int)std::min<size_t>((n + 1023) / 1024, 2048);
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adam_seg_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, step_state, seg_of_chunk, seg_scratch, beta1, beta2,
-                     eps);
+  hipLaunchKernelGGL(adam_seg_kernel<false>, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, step_state, seg_of_chunk, seg_scratch, beta1,
+                     beta2, eps, (float*)nullptr, 0.f);
   return check_launch("adam_seg_kernel");
+}
+
+// the same grid, the EMA instance of the pass (ema.hip); om = 1 - decay
+int launch_adam_seg_ema(float* p, const float* g, float* m, float* v, size_t n, const int32_t* step_state, const int32_t* seg_of_chunk,
+                        const float* seg_scratch, float beta1, float beta2, float eps, float* ema, float om, hipStream_t s) {
+  int blocks = (int)std::min<size_t>((n + 1023) / 1024, 2048);
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adam_seg_kernel<true>, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, step_state, seg_of_chunk, seg_scratch, beta1,
+                     beta2, eps, ema, om);
+  return check_launch("adam_seg_kernel<ema>");
+}
+
+// adam_prep_seg_kernel on its own, for ema.hip (the prep kernels of the other three forms live in loss_scale.hip / lr_device.hip)
+int launch_adam_prep_seg(int32_t* step_state, const float* norm, float max_norm, float lr, float beta1, float beta2,
+                         const int32_t* seg_first, float* seg_scratch, int n_seg, hipStream_t s) {
+  hipLaunchKernelGGL(adam_prep_seg_kernel, dim3(1), dim3(256), 0, s, step_state, norm, max_norm, lr, beta1, beta2, seg_first, seg_scratch,
+                     n_seg);
+  return check_launch("adam_prep_seg_kernel");
 }
 
 }  // namespace ms
@@ -1994,8 +2033,8 @@ int ms_adam_step_segmented(float* p, const float* g, float* m, float* v, size_t 
   if (rc) return rc;
   int blocks = (int)std::min<size_t>((n + 1023) / 1024, 2048);
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adam_seg_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, step_state, seg_of_chunk,
-                     seg_scratch, beta1, beta2, eps);
+  hipLaunchKernelGGL(adam_seg_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, step_state, seg_of_chunk,
+                     seg_scratch, beta1, beta2, eps, (float*)nullptr, 0.f);
   return check_launch("adam_seg_kernel");
 }
 

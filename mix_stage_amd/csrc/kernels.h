@@ -295,6 +295,23 @@ int launch_colsum_finalize(const float* colpart, float* out, int B, int C, hipSt
 // element pass of the segmented Adam step (elementwise.hip: adam_seg_kernel), behind a prep kernel the caller has launched
 int launch_adam_seg(float* p, const float* g, float* m, float* v, size_t n, const int32_t* step_state, const int32_t* seg_of_chunk,
                     const float* seg_scratch, float beta1, float beta2, float eps, hipStream_t s);
+// ... and its EMA instance (adam_seg_kernel<true>): ema' = fma(om, p' - ema, ema) for every element the pass updates, om = 1 - decay
+int launch_adam_seg_ema(float* p, const float* g, float* m, float* v, size_t n, const int32_t* step_state, const int32_t* seg_of_chunk,
+                        const float* seg_scratch, float beta1, float beta2, float eps, float* ema, float om, hipStream_t s);
+// the four prep kernels on their own, one launch each, for ms_adam_step_segmented_ema (ema.hip): elementwise.hip (lr by value),
+// lr_device.hip (lr word), loss_scale.hip (loss scale), lr_device.hip (both).  No argument checks: the caller has made them
+int launch_adam_prep_seg(int32_t* step_state, const float* norm, float max_norm, float lr, float beta1, float beta2,
+                         const int32_t* seg_first, float* seg_scratch, int n_seg, hipStream_t s);
+int launch_adam_prep_seg_lr(int32_t* step_state, const float* norm, float max_norm, const float* lr_dev, float beta1, float beta2,
+                            const int32_t* seg_first, float* seg_scratch, int n_seg, hipStream_t s);
+int launch_adam_prep_seg_scaled(int32_t* step_state, float* norm, float max_norm, float lr, float beta1, float beta2,
+                                const int32_t* seg_first, float* seg_scratch, int n_seg, int32_t* ls, int growth_interval,
+                                float min_scale, float max_scale, const int32_t* const* meeting_words, int n_meeting_words,
+                                hipStream_t s);
+int launch_adam_prep_seg_scaled_lr(int32_t* step_state, float* norm, float max_norm, const float* lr_dev, float beta1, float beta2,
+                                   const int32_t* seg_first, float* seg_scratch, int n_seg, int32_t* ls, int growth_interval,
+                                   float min_scale, float max_scale, const int32_t* const* meeting_words, int n_meeting_words,
+                                   hipStream_t s);
 
 // ---- device code shared by the prep kernels of the segmented Adam step: adam_prep_seg_kernel (elementwise.hip, lr by value),
 // adam_prep_seg_scaled_kernel (loss_scale.hip, lr by value, loss scale) and their twins that read lr from a device word

@@ -39,6 +39,16 @@ __global__ void adam_prep_seg_scaled_kernel(int32_t* state, float* norm, float m
     adam_scaled_tail(state, norm, raw, finite, meeting, false, step, max_norm, ls, growth_interval, min_scale, max_scale);
 }
 
+// the prep kernel on its own (ema.hip)
+int launch_adam_prep_seg_scaled(int32_t* step_state, float* norm, float max_norm, float lr, float beta1, float beta2,
+                                const int32_t* seg_first, float* seg_scratch, int n_seg, int32_t* ls, int growth_interval,
+                                float min_scale, float max_scale, const int32_t* const* meeting_words, int n_meeting_words,
+                                hipStream_t s) {
+  hipLaunchKernelGGL(adam_prep_seg_scaled_kernel, dim3(1), dim3(256), 0, s, step_state, norm, max_norm, lr, beta1, beta2, seg_first,
+                     seg_scratch, n_seg, ls, growth_interval, min_scale, max_scale, meeting_words, n_meeting_words);
+  return check_launch("adam_prep_seg_scaled_kernel");
+}
+
 }  // namespace ms
 
 using namespace ms;

@@ -72,6 +72,23 @@ __global__ void adam_prep_seg_scaled_lr_kernel(int32_t* state, float* norm, floa
     adam_scaled_tail(state, norm, raw, finite, meeting, adam_lr_bad(lr), step, max_norm, ls, growth_interval, min_scale, max_scale);
 }
 
+// the two prep kernels on their own (ema.hip)
+int launch_adam_prep_seg_lr(int32_t* step_state, const float* norm, float max_norm, const float* lr_dev, float beta1, float beta2,
+                            const int32_t* seg_first, float* seg_scratch, int n_seg, hipStream_t s) {
+  hipLaunchKernelGGL(adam_prep_seg_lr_kernel, dim3(1), dim3(256), 0, s, step_state, norm, max_norm, lr_dev, beta1, beta2, seg_first,
+                     seg_scratch, n_seg);
+  return check_launch("adam_prep_seg_lr_kernel");
+}
+
+int launch_adam_prep_seg_scaled_lr(int32_t* step_state, float* norm, float max_norm, const float* lr_dev, float beta1, float beta2,
+                                   const int32_t* seg_first, float* seg_scratch, int n_seg, int32_t* ls, int growth_interval,
+                                   float min_scale, float max_scale, const int32_t* const* meeting_words, int n_meeting_words,
+                                   hipStream_t s) {
+  hipLaunchKernelGGL(adam_prep_seg_scaled_lr_kernel, dim3(1), dim3(256), 0, s, step_state, norm, max_norm, lr_dev, beta1, beta2, seg_first,
+                     seg_scratch, n_seg, ls, growth_interval, min_scale, max_scale, meeting_words, n_meeting_words);
+  return check_launch("adam_prep_seg_scaled_lr_kernel");
+}
+
 }  // namespace ms
 
 using namespace ms;

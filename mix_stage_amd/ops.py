@@ -1608,6 +1608,45 @@ def adam_step_segmented_scaled_lr(p, g, m, v, norm, max_norm, lr_word, beta1, be
         'ms_adam_step_segmented_scaled_lr')
 
 
+def check_ema_decay(decay, who):
+  """The decay of a weight average as a float in [0, 1); ValueError otherwise (NaN, infinite, negative, 1 or more)."""
+  try:
+    d = float(decay)
+  except (TypeError, ValueError):
+    raise ValueError('%s: ema_decay must be a float in [0, 1), got %r' % (who, decay))
+  if not (d >= 0.0 and d < 1.0) or not (ctypes.c_float(d).value < 1.0):     # (the kernel argument is fp32)
+    raise ValueError('%s: ema_decay must be finite and in [0, 1), got %r' % (who, decay))
+  return d
+
+
+def adam_step_segmented_ema(p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, step_state, seg_of_chunk, seg_first, seg_scratch,
+                            ema, ema_decay, lr_word=None, loss_scale_state=None, growth_interval=0, min_scale=1.0, max_scale=1.0,
+                            meeting_table=None):
+  """The segmented Adam step of whichever form is configured -- lr by value, or read from `lr_word` when it is given (`lr` is then
+  ignored); unscaled, or with the loss scale of `loss_scale_state` when it is given -- that also moves `ema`, an fp32 device
+  tensor with the layout of `p`, inside the element pass: ema += (1 - ema_decay) * (p_new - ema) for every element the step
+  updates (include/mixstage.h: ms_adam_step_segmented_ema).  p, m, v and the state words get the bits of the form without it."""
+  if not (torch.is_tensor(ema) and ema.is_cuda and ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() == p.numel()):
+    raise TypeError('adam_step_segmented_ema: ema is a contiguous fp32 device tensor with as many elements as p')
+  d = check_ema_decay(ema_decay, 'adam_step_segmented_ema')
+  if lr_word is not None:
+    _check_lr_word(lr_word, 'adam_step_segmented_ema')
+  if meeting_table is not None and (meeting_table.dtype != torch.int64 or not meeting_table.is_cuda):
+    raise TypeError('adam_step_segmented_ema: meeting_table is an int64 device tensor of addresses')
+  if loss_scale_state is not None and (loss_scale_state.dtype != torch.int32 or loss_scale_state.numel() != 8
+                                       or not loss_scale_state.is_cuda):
+    raise TypeError('adam_step_segmented_ema: loss_scale_state is 8 int32 words on the device')
+  check(lib().ms_adam_step_segmented_ema(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(norm), max_norm,
+                                         0.0 if lr is None else float(lr), _ptr(lr_word) if lr_word is not None else None,
+                                         beta1, beta2, eps, _ptr(step_state), _ptr(seg_of_chunk), _ptr(seg_first),
+                                         _ptr(seg_scratch), seg_first.numel(),
+                                         _ptr(loss_scale_state) if loss_scale_state is not None else None, int(growth_interval),
+                                         float(min_scale), float(max_scale),
+                                         _ptr(meeting_table) if meeting_table is not None else None,
+                                         meeting_table.numel() if meeting_table is not None else 0, _ptr(ema), d, _stream()),
+        'ms_adam_step_segmented_ema')
+
+
 def write_floats(dst, values):
   """Up to 8 host floats -> the fp32 device tensor `dst`, BY VALUE through a kernel's arguments on the current stream
   (ms_write_floats): the values are copied when the launch is enqueued, so a host that runs ahead of the device cannot overwrite

@@ -29,6 +29,33 @@ class StyleTransferSampler:
     self.speaker = speaker_names or [str(i) for i in range(num_styles)]
     self.use_graphs = use_graphs
     self._graphs = {}
+    self._tensors = None
+
+  def _weights_version(self):
+    """Sum of the version counters of the model's parameters and buffers: moves when torch changed one of them in place
+    (load_weights / load_state_dict, a manual edit)."""
+    if self._tensors is None:
+      self._tensors = list(self.model.parameters()) + list(self.model.buffers())
+    return sum(t._version for t in self._tensors)
+
+  def _replay(self, entry):
+    """Replay a captured forward on the weights the model holds NOW.  Under a trainer the kernels read operands derived from the
+    weights (16-bit copies, chain weight streams) from buffers that are rebuilt when a weight's version counter moved -- but a
+    captured graph holds no such comparison, it reads whatever the buffers held.  The trainer rebuilds them in place behind its
+    own updates (a step, ema_weights()); an edit torch made is noticed here, and the buffers of every parameter storage are
+    rebuilt in place before the replay, so the graph's pointers stay valid."""
+    v = self._weights_version()
+    if v != entry['version']:
+      from . import ops
+      seen = set()
+      for p in self.model.parameters():
+        if p.is_cuda:
+          sp = p.untyped_storage().data_ptr()
+          if sp not in seen:
+            seen.add(sp)
+            ops.refresh_prepared_weights(p)
+      entry['version'] = v
+    entry['graph'].replay()
 
   def _kwargs(self, style, T):
     return dict(input_modalities=self.model.input_modalities, desc='test', sample_flag=1, description='test',
@@ -76,7 +103,7 @@ class StyleTransferSampler:
       st = entry['static']
       for k, src in (('audio', audio), ('labels', labels), ('pose', pose), ('style', style)):
         st[k].copy_(src, non_blocking=True)
-      entry['graph'].replay()
+      self._replay(entry)
       results.append((name, entry['y_cap'].clone(), [l.clone() for l in entry['losses']]))
     # an in-launch meeting that gave up (the launch did not have the GPU to itself) poisons its outputs with NaN: outside a
     # training step nobody else looks at the error word, so every interval ends with the (synchronising) check -- the caller is
@@ -161,7 +188,7 @@ class StyleTransferSampler:
       st = entry['static']
       for k, src in (('audio', audio), ('labels', labels), ('pose', pose), ('style', style)):
         st[k].copy_(src, non_blocking=True)
-      entry['graph'].replay()
+      self._replay(entry)
       results.append((name, entry['y_cap'].clone(), [l.clone() for l in entry['losses']]))
     from . import ops16
     ops16.check_meetings()                  # as sample_interval: a meeting that gave up poisons its outputs, nobody else looks
@@ -180,6 +207,6 @@ class StyleTransferSampler:
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
       y_cap, losses = self._forward(st['audio'], st['labels'], st['pose'], st['style'])
-    entry = dict(graph=g, static=st, y_cap=y_cap, losses=[l for l in losses])
+    entry = dict(graph=g, static=st, y_cap=y_cap, losses=[l for l in losses], version=self._weights_version())
     self._graphs[key] = entry
     return entry

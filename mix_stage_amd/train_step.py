@@ -15,6 +15,8 @@ MI355X-first structure:
     (bn_sync='local'); host-side random decisions come from identically seeded CPU generators so all
     ranks take the same D-vs-G branch (gan.py:105) and curriculum branch (JL:127).
 """
+import collections
+import contextlib
 import copy
 import os
 import weakref
@@ -98,10 +100,17 @@ class FlatAdam:
   device_lr=True: the learning rate lives in `lr_word`, one fp32 word on the device that the prep kernel reads when it runs
   (ms_adam_step_segmented_lr / _scaled_lr), so a step captured into a HIP graph follows set_lr() from replay to replay.  With
   False (default) lr is a by-value kernel argument: assigning `self.lr` works for eager launches only, a captured step keeps the
-  value it was captured with."""
+  value it was captured with.
+  ema_decay (None: off, the four entry points above run as before): a float in [0, 1).  `self.ema` is then an fp32 buffer with the
+  layout of `flat_p`, started as a copy of it, and every applied step moves it inside the Adam element pass
+  (ms_adam_step_segmented_ema: ema += (1 - ema_decay) * (p_new - ema), no extra launch).  A refused step, an overflow skip and a
+  parameter that has not had a gradient yet leave it alone.  The decay is a by-value kernel argument, frozen into a captured step.
+  Writing other weights into the parameters (load_state_dict, checkpoint.load_weights) does NOT touch the average: call
+  ema_reset() to restart it from the new weights, or set_optimizer_state() to restore one that was saved with them."""
 
   def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_norm=1.0, order_last=(), order_first=(), loss_scale=None,
-               device_lr=False):
+               device_lr=False, ema_decay=None):
+    self.ema_decay = ops.check_ema_decay(ema_decay, 'FlatAdam(ema_decay=)') if ema_decay is not None else None
     self.params = [p for p in params if p.requires_grad]
     if not self.params:
       raise ValueError('no trainable parameters')
@@ -171,6 +180,7 @@ class FlatAdam:
     self.seg_scratch = torch.zeros(2 * len(self.params), dtype=torch.float32, device=dev)
     self.host_step = 0                                 # optimizer steps executed so far
     self._grad_versions = [g._version for g in self._grad_views]
+    self.ema = self.flat_p.clone() if self.ema_decay is not None else None
 
   def zero_grad(self):
     self.flat_g.zero_()
@@ -225,6 +235,50 @@ class FlatAdam:
     self.host_step = 0
     if self.loss_scale is not None:
       self.set_loss_scale_state(self.loss_scale.initial_state())
+    if self.ema is not None:
+      self.ema.copy_(self.flat_p)
+
+  def ema_reset(self):
+    """The average restarts from the current weights (after loading weights, which leaves it alone).  Not inside a capture."""
+    if self.ema is None:
+      raise RuntimeError('FlatAdam.ema_reset(): constructed without ema_decay')
+    if torch.cuda.is_current_stream_capturing():
+      raise RuntimeError('FlatAdam.ema_reset inside a stream capture: the copy would become part of the captured step')
+    self.ema.copy_(self.flat_p)
+
+  # ---- state for a caller that checkpoints ---------------------------------------------------------------------
+  def optimizer_state(self):
+    """dict of CPU tensors and ints: exp_avg, exp_avg_sq, step_state (words 0 and 3: the step clock and the refused-step count),
+    host_first, host_step, ema (None without an average), total.  A synchronising host read.  The learning rate and the loss scale
+    have their own pairs (lr / set_lr, loss_scale_state / set_loss_scale_state); the weights are the model's state_dict."""
+    w = self.step_state.cpu()
+    return dict(exp_avg=self.exp_avg.cpu(), exp_avg_sq=self.exp_avg_sq.cpu(), step_state=(int(w[0]), int(w[3])),
+                host_first=list(self.host_first), host_step=int(self.host_step),
+                ema=self.ema.cpu() if self.ema is not None else None, total=int(self.total))
+
+  def set_optimizer_state(self, d):
+    """Write back what optimizer_state() returned, on an optimizer over the same parameters in the same order.  Not inside a
+    capture.  ValueError: the sizes differ, or one of the two has an average and the other has none."""
+    if torch.cuda.is_current_stream_capturing():
+      raise RuntimeError('FlatAdam.set_optimizer_state inside a stream capture')
+    if int(d['total']) != self.total or len(d['host_first']) != len(self.params):
+      raise ValueError('set_optimizer_state: the state holds %d elements in %d parameters, this optimizer %d in %d'
+                       % (int(d['total']), len(d['host_first']), self.total, len(self.params)))
+    for k in ('exp_avg', 'exp_avg_sq') + (('ema',) if d['ema'] is not None else ()):
+      if d[k].numel() != self.total or d[k].dtype != torch.float32:
+        raise ValueError('set_optimizer_state: %s is not %d fp32 values' % (k, self.total))
+    if (d['ema'] is None) != (self.ema is None):
+      raise ValueError('set_optimizer_state: the state was taken %s an average (ema_decay), this optimizer is built %s one'
+                       % (('without', 'with') if d['ema'] is None else ('with', 'without')))
+    self.exp_avg.copy_(d['exp_avg'].reshape(-1))
+    self.exp_avg_sq.copy_(d['exp_avg_sq'].reshape(-1))
+    if self.ema is not None:
+      self.ema.copy_(d['ema'].reshape(-1))
+    step, refused = d['step_state']
+    self.step_state.copy_(torch.tensor([int(step), 0, 0, int(refused)], dtype=torch.int32))
+    self.host_first = [int(x) for x in d['host_first']]
+    self.seg_first.copy_(torch.tensor(self.host_first, dtype=torch.int32))
+    self.host_step = int(d['host_step'])
 
   # ---- loss scaling (fp16 training) --------------------------------------------------------------------------
   def seed(self):
@@ -280,7 +334,16 @@ class FlatAdam:
     ops.grad_norm(self.flat_g, self.norm, self.partials)
     # device_lr: the same launches with lr read from the device word (same bits for the same lr)
     lr = self.lr_word if self.device_lr else self.lr
-    if self.loss_scale is None:
+    if self.ema is not None:
+      # one entry point for the four forms below: the same prep launch, the element pass also moves the average
+      rule = self.loss_scale
+      ops.adam_step_segmented_ema(
+          self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm, self.max_norm, None if self.device_lr else self.lr,
+          self.betas[0], self.betas[1], self.eps, self.step_state, self.seg_of_chunk, self.seg_first, self.seg_scratch,
+          self.ema, self.ema_decay, lr_word=self.lr_word, loss_scale_state=self.ls_state if rule is not None else None,
+          growth_interval=rule.growth_interval if rule is not None else 0, min_scale=rule.min if rule is not None else 1.0,
+          max_scale=rule.max if rule is not None else 1.0, meeting_table=self.meeting_table if rule is not None else None)
+    elif self.loss_scale is None:
       (ops.adam_step_segmented_lr if self.device_lr else ops.adam_step_segmented)(
           self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm, self.max_norm, lr,
           self.betas[0], self.betas[1], self.eps, self.step_state, self.seg_of_chunk, self.seg_first,
@@ -319,11 +382,20 @@ class MixStageTrainStep:
   lr_schedule (None: the learning rate is the constant `lr`, as a by-value kernel argument): a float gamma -- the reference's
   ExponentialLR(gamma), TR:311-313 -- or a schedule object (lr_schedule.py).  Both optimizers then keep their learning rate in a
   device word that the captured steps read at every replay; epoch_end() steps the schedule (TR:499-500), set_lr() sets explicit
-  values.  Every rank of a data-parallel job computes the same host values, nothing is exchanged."""
+  values.  Every rank of a data-parallel job computes the same host values, nothing is exchanged.
+  ema_decay (None: off, nothing changes): a float in [0, 1) keeps an exponential moving average of the GENERATOR's parameters,
+  moved by every applied G-step inside its Adam launch (FlatAdam); D-steps, refused steps and overflow skips never move it, and the
+  BatchNorm buffers -- running statistics, moving averages already -- are not averaged.  The decay is a by-value kernel argument:
+  it is constant, and frozen into the captured steps.  ema_state_dict() reads the average, ema_weights() runs the model on it,
+  checkpoint.save_weights(..., ema=True) writes it; optimizer_state() carries it with the moments and the step clocks.
+  checkpoint.load_weights leaves the average alone: call optim_G.ema_reset() behind it to restart the average from those weights."""
 
   def __init__(self, model, lr=1e-4, clip=1.0, use_graphs=True, process_group=None, time_steps=64, overlap_wgrad=False,
-               bn_sync='local', overlap_allreduce=False, grad_buckets=None, grad_exchange='fp32', loss_scale=None, lr_schedule=None):
+               bn_sync='local', overlap_allreduce=False, grad_buckets=None, grad_exchange='fp32', loss_scale=None, lr_schedule=None,
+               ema_decay=None):
     self.model = model
+    self.ema_decay = ops.check_ema_decay(ema_decay, 'MixStageTrainStep(ema_decay=)') if ema_decay is not None else None
+    self._in_ema_weights = False
     # one scheduler per optimizer, as in the reference (TR:311-313): each is chained on its own network's learning rate
     sched = as_lr_schedule(lr_schedule)
     self.lr_schedules = (sched, copy.deepcopy(sched)) if sched is not None else None
@@ -401,7 +473,7 @@ class MixStageTrainStep:
             if n.split('.')[0] in ('text_encoder', 'pose_encoder', 'style_dec', 'style_dec_gr', 'concat_encoder', 'smoothen')]
     early = [p for n, p in model.G.named_parameters() if n.split('.')[0] in ('decoder', 'logits', 'classify_cluster')]
     self.optim_G = FlatAdam(model.G.parameters(), lr=lr, max_norm=clip, order_last=idle, order_first=early, loss_scale=self.loss_scale_rule,
-                            device_lr=self.lr_schedules is not None)
+                            device_lr=self.lr_schedules is not None, ema_decay=self.ema_decay)
     self.optim_D = FlatAdam(model.D.parameters(), lr=lr, max_norm=clip, loss_scale=self.loss_scale_rule,
                             device_lr=self.lr_schedules is not None)
     self.use_graphs = use_graphs
@@ -410,6 +482,8 @@ class MixStageTrainStep:
     self.world = _dp_world(process_group)          # > 1: the data-parallel form of the step (see _single_rank_dp)
     if self.world > 1:
       broadcast_from_rank0([self.optim_G.flat_p, self.optim_D.flat_p] + [b for b in model.buffers()], process_group)
+      if self.ema_decay is not None:
+        self.optim_G.ema_reset()          # the average starts from the weights every rank starts from
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
       # ranks that share a GPU (test set-ups): a launch whose workgroups wait for each other needs the device to itself
       # (physical identity: launchers that set HIP_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES per rank make every rank see index 0)
@@ -622,6 +696,8 @@ class MixStageTrainStep:
     the words on the caller's current stream, the stream step() launches or replays on -- call them between two steps, from the
     thread and under the stream that calls step(); stream order does the rest (no synchronisation)."""
     m = self.model
+    if self._in_ema_weights:
+      raise RuntimeError('MixStageTrainStep.step() inside ema_weights(): the parameters hold the average, leave the context first')
     self._ensure_train_mode()
     # (module-level switch of the ops: another trainer built in this process may have set it differently)
     ops.set_bn_sync(self.bn_sync == 'global', self.process_group)
@@ -897,6 +973,81 @@ class MixStageTrainStep:
     self.lr_epoch = int(d['epoch'])
     self.optim_G.set_lr(d['lr_G'])
     self.optim_D.set_lr(d['lr_D'])
+
+  # ---- the generator's moving average, optimizer state -------------------------------------------------------
+  def _need_ema(self, who):
+    if self.ema_decay is None:
+      raise RuntimeError('MixStageTrainStep.%s: constructed without ema_decay' % who)
+
+  def ema_state_dict(self):
+    """model.G.state_dict() with the parameters taken from the average: an ordered dict of the same names, as detached copies on
+    the parameters' device.  Buffers (BatchNorm running statistics and batch counts) are the live ones.  Synchronises."""
+    self._need_ema('ema_state_dict')
+    opt = self.optim_G
+    src = opt.flat_p if self._in_ema_weights else opt.ema        # (inside ema_weights() the two have changed places)
+    avg = {id(p): src[o:o + p.numel()].view_as(p) for p, o in zip(opt.params, opt.offsets)}
+    by_name = {n: avg[id(p)] for n, p in self.model.G.named_parameters() if id(p) in avg}
+    out = collections.OrderedDict()
+    for name, v in self.model.G.state_dict().items():
+      out[name] = (by_name[name] if name in by_name else v).detach().clone()
+    torch.cuda.synchronize()
+    return out
+
+  def _exchange_ema(self):
+    opt = self.optim_G
+    with torch.no_grad():
+      tmp = opt.flat_p.clone()
+      opt.flat_p.copy_(opt.ema)
+      opt.ema.copy_(tmp)
+    # The parameters are .data views with version counters of their own: the copy above moved flat_p's counter only, and the
+    # caches derived from the weights (prepared data-gradient weights, 16-bit copies, chain and eval-chain weight streams) compare
+    # the parameters' counters.  Rebuild all of them explicitly, in place: a sampler graph captured earlier reads the same buffers.
+    ops.refresh_prepared_weights(opt.flat_p)
+    opt.seen_version = opt._param_versions()
+
+  @contextlib.contextmanager
+  def ema_weights(self):
+    """Context manager: inside it G's parameters hold the average (the live weights wait in the average's buffer), and every cache
+    derived from them has been rebuilt -- evaluate or sample the model as usual.  D, every buffer and the optimizer's moments are
+    untouched.  On exit the live weights are back bit for bit, the average likewise, and the derived caches follow.  step() inside
+    raises RuntimeError, and so does entering twice.  Not inside a capture."""
+    self._need_ema('ema_weights')
+    if self._in_ema_weights:
+      raise RuntimeError('MixStageTrainStep.ema_weights() is not re-entrant')
+    if torch.cuda.is_current_stream_capturing():
+      raise RuntimeError('MixStageTrainStep.ema_weights inside a stream capture')
+    self._exchange_ema()
+    self._in_ema_weights = True
+    try:
+      yield self
+    finally:
+      self._in_ema_weights = False
+      self._exchange_ema()
+
+  def optimizer_state(self):
+    """{'G': ..., 'D': ...}: FlatAdam.optimizer_state() of both networks (moments, step clocks, the average) for a caller that
+    checkpoints.  A resumable checkpoint is this plus model.state_dict(), lr_state(), loss_scale() and the caller's own host
+    state: the host RNG, model.G.thresh and the lambda scheduler.  Synchronises."""
+    if self._in_ema_weights:
+      raise RuntimeError('MixStageTrainStep.optimizer_state() inside ema_weights()')
+    return {'G': self.optim_G.optimizer_state(), 'D': self.optim_D.optimizer_state()}
+
+  def set_optimizer_state(self, d):
+    """Restore what optimizer_state() returned, on a trainer over the same model built with the same options.  Between steps, not
+    inside a capture; ValueError on a size mismatch or when only one side has an average."""
+    if self._in_ema_weights:
+      raise RuntimeError('MixStageTrainStep.set_optimizer_state() inside ema_weights()')
+    for k, opt in (('G', self.optim_G), ('D', self.optim_D)):      # (check both before either is written)
+      if int(d[k]['total']) != opt.total or len(d[k]['host_first']) != len(opt.params):
+        raise ValueError('set_optimizer_state: the %s state does not fit this trainer (%d elements against %d)'
+                         % (k, int(d[k]['total']), opt.total))
+      if (d[k]['ema'] is None) != (opt.ema is None):
+        raise ValueError('set_optimizer_state: the %s state and this trainer differ in having an average (ema_decay)' % k)
+    self.optim_G.set_optimizer_state(d['G'])
+    self.optim_D.set_optimizer_state(d['D'])
+    # the refused steps the state has already counted were reported by the run that saved it
+    self._health_events = []
+    self._health_seen = int(d['G']['step_state'][1]) + int(d['D']['step_state'][1])
 
   def loss_scale(self):
     """{'G': dict(scale, good_steps, overflow_skips), 'D': ...} of the two networks' loss scales (synchronises)."""
