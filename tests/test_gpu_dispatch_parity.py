@@ -6,7 +6,8 @@ case that drifts to another kernel fails and names the labels it got), and compa
   fp32 / bf16x6   the oracle's ConvNormRelu (or conv) in float64, the bars of test_gpu_kernels._conv_block_case: forward
                   <= 2e-5, dx / dw / dgamma / dbeta <= 1e-4 relative to the tensor's max-abs, running statistics <= 1e-5,
                   the conv bias gradient (true value 0 before BatchNorm) ~ 0.
-  bf16 / fp16     test_gpu_kernels16._case: fp64 on the same 16-bit-rounded operands, its bars (returned with the values).
+  bf16 / fp16     test_gpu_kernels16._case: fp64 on the same 16-bit-rounded operands, its bars (returned with the values);
+                  bars='dtype': bf16 keeps the bars it had, the fp16 entries get the fp16-sized ones.
 
 LeakyReLU kinks: at B = 32 some pre-activation is almost always within fp32 rounding of 0 and takes the other slope than in
 fp64.  The fp64 reference therefore takes its slope mask from the sign of the device output, and the test asserts that the
@@ -223,7 +224,7 @@ def _run_16(e, labels, keep=None):
     measured = _case(nd, e['B'], e['cin'], e['cout'], e['groups'], e['k'], e['s'], e['p'], H, W, MODES[e['mode']],
                      IN_MODES[e['in_mode']], e['out_f32'], dt=dt, seed=zlib.crc32(e['id'].encode()) % 1000,
                      mask='device' if e['mode'] in ('BN_TRAIN', 'LRELU') else 'exact', ref_dev=_ref_device(e),
-                     bn_folded=e['folded'], keep=keep)
+                     bn_folded=e['folded'], keep=keep, bars='dtype')
   return measured
 
 
