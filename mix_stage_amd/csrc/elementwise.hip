@@ -1,6 +1,6 @@
 // HBM-bound kernels of the path: BatchNorm statistics/apply/backward, activation backward, the
 // AudioEncoder time-lerp, the softmax mixture of the M sub-generators, cross entropy, pose velocity,
-// layout transposes, L1 losses, and the trainer tail (global grad norm + clipped Adam).
+// layout transposes, L1 losses, and the global gradient norm of the trainer tail (the clipped Adam step: adam.hip).
 // All reductions run in a fixed order (no float atomics) -> bitwise reproducible.
 #include <algorithm>
 
@@ -1270,162 +1270,6 @@ __global__ __launch_bounds__(256) void lp_pair_bwd_kernel(const float* __restric
   }
 }
 
-// Adam (torch.optim.Adam defaults: no amsgrad, no weight decay) with clip_grad_norm_ folded in.
-// state words: [0] step (int32), [1] clip coef (NaN: the gradient norm was not finite, the update is skipped), [2] step_size = lr/bc1, [3] sqrt(bc2)
-__global__ void adam_prep_kernel(int32_t* state, const float* norm, float max_norm, float lr, float beta1, float beta2) {
-  const int step = state[0] + 1;
-  state[0] = step;
-  float* f = reinterpret_cast<float*>(state);
-  float coef = 1.f;
-  if (norm) {
-    coef = max_norm / (norm[0] + 1e-6f);
-    if (coef > 1.f) coef = 1.f;
-    if (!(fabsf(norm[0]) <= 3.0e38f)) coef = __builtin_nanf("");   // non-finite gradient: adam_kernel leaves p, m, v untouched
-  }
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  f[1] = coef;
-  f[2] = (float)((double)lr / bc1);
-  f[3] = (float)sqrt(bc2);
-}
-
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, size_t n, const int32_t* __restrict__ state,
-                                                   float beta1, float beta2, float eps) {
-  const float* f = reinterpret_cast<const float*>(state);
-  const float coef = f[1], step_size = f[2], bc2s = f[3];
-  if (coef != coef) return;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    const float gi = g[i] * coef;
-    const float mi = m[i] + (1.f - beta1) * (gi - m[i]);
-    const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    p[i] -= step_size * (mi / (sqrtf(vi) / bc2s + eps));
-  }
-}
-
-// Segmented form: torch.optim.Adam keeps one step count PER PARAMETER, started when the parameter first receives a
-// gradient, and skips parameters that never had one.  seg_first[s] = global step (1-based) of the segment's first
-// gradient, or -1; seg_scratch[2s..2s+1] = (lr/bc1, sqrt(bc2)) of the segment for this step (0,0 = inactive).
-__global__ void adam_prep_seg_kernel(int32_t* state, const float* norm, float max_norm, float lr, float beta1, float beta2,
-                                     const int32_t* __restrict__ seg_first, float* __restrict__ seg_scratch, int n_seg) {
-  const int step = state[0] + 1;
-  for (int sidx = threadIdx.x; sidx < n_seg; sidx += blockDim.x) {
-    const int first = seg_first[sidx];
-    float ss = 0.f, b2 = 0.f;
-    if (first >= 1 && first <= step) {
-      const double t = (double)(step - first + 1);
-      ss = adam_seg_step_size(lr, beta1, t);      // (kernels.h: one definition for every prep kernel of this step)
-      b2 = adam_seg_bc2(beta2, t);
-    }
-    seg_scratch[2 * sidx] = ss;
-    seg_scratch[2 * sidx + 1] = b2;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    state[0] = step;
-    float coef = 1.f;
-    if (norm) {
-      // (clip coefficient and health words: kernels.h, shared with the prep kernels of loss_scale.hip and lr_device.hip)
-      coef = adam_clip_coef(max_norm, norm[0]);
-      // A non-finite gradient norm (a launch whose in-launch meeting timed out poisons its output with NaN, and the NaN reaches
-      // every gradient behind it) must not reach the weights or the moments: the update of this step is SKIPPED on the device --
-      // word 2 flags the step, word 3 counts such steps (MixStageTrainStep reads both with the losses); the step clocks advance
-      // as if the step had had a zero gradient and frozen moments.
-      // (a learning rate that is a device word can refuse the step as well: lr_device.hip)
-      const bool bad = !adam_norm_finite(norm[0]);
-      adam_flag_step(state, bad);
-    }
-    reinterpret_cast<float*>(state)[1] = coef;
-  }
-}
-
-// The element pass is written once and instantiated twice: adam_seg_kernel<false> is the pass as it always was (`e` and `om` are
-// passed as NULL / 0 and never read: every statement that names them is compiled out), adam_seg_kernel<true> also moves an
-// exponential moving average of the weights: e' = fma(om, pn - e, e), om = 1 - decay, one more 16-byte load and store per lane
-// next to the seven of the pass.  An element the pass skips (refused step, inactive segment) keeps its `e`.
-template <bool EMA>
-__global__ __launch_bounds__(256) void adam_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, size_t n, const int32_t* __restrict__ state,
-                                                       const int32_t* __restrict__ seg_of_chunk,
-                                                       const float* __restrict__ seg_scratch, float beta1, float beta2,
-                                                       float eps, float* __restrict__ e, float om) {
-  const float coef = reinterpret_cast<const float*>(state)[1];
-  if (state[2]) return;                        // non-finite gradient norm: no update (adam_prep_seg_kernel)
-  // 16 bytes per lane and stream, two vectors per thread in flight (7 streams over the 60 MB of live parameters: dword accesses
-  // ran at 5.4 TB/s); a 64-element chunk belongs to one segment, so a vector does too.  n is a multiple of 64 (FlatAdam's layout);
-  // the buffers are 256-byte aligned
-  // the roundings are spelled out (explicit fma, contraction off): the vector path and the scalar fallback below give the same bits
-  // for the same element -- left to the compiler, the fallback rounded the products of mn and vn separately and the vector path did not
-  auto upd = [&](float pi, float gr, float mo, float vo, float step_size, float bc2s, float& mn, float& vn) {
-#pragma clang fp contract(off)
-    const float gi = gr * coef;
-    mn = fmaf(1.f - beta1, fmaf(gr, coef, -mo), mo);
-    vn = fmaf(beta2, vo, gi * ((1.f - beta2) * gi));
-    return fmaf(-step_size, mn / (sqrtf(vn) / bc2s + eps), pi);
-  };
-  // the average: the difference is rounded, then one fma (contraction off, as above: both paths give the same bits)
-  auto avg = [&](float pn, float eo) {
-#pragma clang fp contract(off)
-    const float t = pn - eo;
-    return fmaf(om, t, eo);
-  };
-  if ((n & 3) == 0 && ((((size_t)p | (size_t)g | (size_t)m | (size_t)v | (EMA ? (size_t)e : (size_t)0)) & 15) == 0)) {
-    const size_t n4 = n >> 2, stride = (size_t)gridDim.x * 256;
-    float4* p4 = reinterpret_cast<float4*>(p);
-    const float4* g4 = reinterpret_cast<const float4*>(g);
-    float4* m4 = reinterpret_cast<float4*>(m);
-    float4* v4 = reinterpret_cast<float4*>(v);
-    float4* e4 = reinterpret_cast<float4*>(e);
-    for (size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x; i0 < n4; i0 += 2 * stride) {
-      float4 pv[2], gv[2], mv[2], vv[2], ev[2];
-      float ss[2], bc[2];
-      bool on[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const size_t i = i0 + u * stride;
-        on[u] = i < n4;
-        const int sidx = seg_of_chunk[min(i, n4 - 1) >> 4];
-        ss[u] = seg_scratch[2 * sidx]; bc[u] = seg_scratch[2 * sidx + 1];
-        on[u] = on[u] && bc[u] != 0.f;         // never received a gradient: torch.optim.Adam skips it
-        if (on[u]) {
-          pv[u] = p4[i]; gv[u] = g4[i]; mv[u] = m4[i]; vv[u] = v4[i];
-          if constexpr (EMA) ev[u] = e4[i];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        if (!on[u]) continue;
-        const size_t i = i0 + u * stride;
-        float4 mn, vn, pn;
-        pn.x = upd(pv[u].x, gv[u].x, mv[u].x, vv[u].x, ss[u], bc[u], mn.x, vn.x);
-        pn.y = upd(pv[u].y, gv[u].y, mv[u].y, vv[u].y, ss[u], bc[u], mn.y, vn.y);
-        pn.z = upd(pv[u].z, gv[u].z, mv[u].z, vv[u].z, ss[u], bc[u], mn.z, vn.z);
-        pn.w = upd(pv[u].w, gv[u].w, mv[u].w, vv[u].w, ss[u], bc[u], mn.w, vn.w);
-        m4[i] = mn; v4[i] = vn; p4[i] = pn;
-        if constexpr (EMA) {
-          float4 en;
-          en.x = avg(pn.x, ev[u].x); en.y = avg(pn.y, ev[u].y); en.z = avg(pn.z, ev[u].z); en.w = avg(pn.w, ev[u].w);
-          e4[i] = en;
-        }
-      }
-    }
-    return;
-  }
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    const int sidx = seg_of_chunk[i >> 6];
-    const float step_size = seg_scratch[2 * sidx], bc2s = seg_scratch[2 * sidx + 1];
-    if (bc2s == 0.f) continue;                 // never received a gradient: torch.optim.Adam skips it
-    float mn, vn;
-    const float pn = upd(p[i], g[i], m[i], v[i], step_size, bc2s, mn, vn);
-    m[i] = mn;
-    v[i] = vn;
-    p[i] = pn;
-    if constexpr (EMA) e[i] = avg(pn, e[i]);
-  }
-}
-
 static inline int red_blocks(size_t n) {
   size_t b = (n + 256 * 8 - 1) / (256 * 8);
   if (b < 1) b = 1;
@@ -1571,34 +1415,6 @@ int launch_colsum_finalize(const float* colpart, float* out, int B, int C, hipSt
   const int nchunk = bwd_chunks(B, C, &bpc);
   hipLaunchKernelGGL(colsum_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, colpart, out, C, nchunk);
   return check_launch("colsum_finalize_kernel");
-}
-
-// the element pass of ms_adam_step_segmented on its own, for a caller that ran a prep kernel of its own (loss_scale.hip)
-int launch_adam_seg(float* p, const float* g, float* m, float* v, size_t n, const int32_t* step_state, const int32_t* seg_of_chunk,
-                    const float* seg_scratch, float beta1, float beta2, float eps, hipStream_t s) {
-  int blocks = (int)std::min<size_t>((n + 1023) / 1024, 2048);
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adam_seg_kernel<false>, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, step_state, seg_of_chunk, seg_scratch, beta1,
-                     beta2, eps, (float*)nullptr, 0.f);
-  return check_launch("adam_seg_kernel");
-}
-
-// the same grid, the EMA instance of the pass (ema.hip); om = 1 - decay
-int launch_adam_seg_ema(float* p, const float* g, float* m, float* v, size_t n, const int32_t* step_state, const int32_t* seg_of_chunk,
-                        const float* seg_scratch, float beta1, float beta2, float eps, float* ema, float om, hipStream_t s) {
-  int blocks = (int)std::min<size_t>((n + 1023) / 1024, 2048);
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adam_seg_kernel<true>, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, step_state, seg_of_chunk, seg_scratch, beta1,
-                     beta2, eps, ema, om);
-  return check_launch("adam_seg_kernel<ema>");
-}
-
-// adam_prep_seg_kernel on its own, for ema.hip (the prep kernels of the other three forms live in loss_scale.hip / lr_device.hip)
-int launch_adam_prep_seg(int32_t* step_state, const float* norm, float max_norm, float lr, float beta1, float beta2,
-                         const int32_t* seg_first, float* seg_scratch, int n_seg, hipStream_t s) {
-  hipLaunchKernelGGL(adam_prep_seg_kernel, dim3(1), dim3(256), 0, s, step_state, norm, max_norm, lr, beta1, beta2, seg_first, seg_scratch,
-                     n_seg);
-  return check_launch("adam_prep_seg_kernel");
 }
 
 }  // namespace ms
@@ -2007,35 +1823,6 @@ int ms_sqnorm(const float* g, size_t n, float* norm_out, float* partials, void* 
   if (rc) return rc;
   hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, nb, norm_out, 1.0f, 1);
   return check_launch("reduce_final_kernel");
-}
-
-int ms_adam_step(float* p, const float* g, float* m, float* v, size_t n, const float* norm, float max_norm, float lr,
-                 float beta1, float beta2, float eps, int32_t* step_state, void* stream) {
-  TimingScope ts((hipStream_t)stream, 0, 0, "ew|ew_adam_step");
-  if (ts.skip()) return 0;
-  hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_state, norm, max_norm, lr, beta1, beta2);
-  int rc = check_launch("adam_prep_kernel");
-  if (rc) return rc;
-  int blocks = (int)std::min<size_t>((n + 1023) / 1024, 2048);
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, step_state, beta1, beta2, eps);
-  return check_launch("adam_kernel");
-}
-
-int ms_adam_step_segmented(float* p, const float* g, float* m, float* v, size_t n, const float* norm, float max_norm, float lr,
-                           float beta1, float beta2, float eps, int32_t* step_state, const int32_t* seg_of_chunk,
-                           const int32_t* seg_first_step, float* seg_scratch, int n_seg, void* stream) {
-  TimingScope ts((hipStream_t)stream, 0, 0, "ew|ew_adam_step_segmented");
-  if (ts.skip()) return 0;
-  hipLaunchKernelGGL(adam_prep_seg_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, step_state, norm, max_norm, lr, beta1,
-                     beta2, seg_first_step, seg_scratch, n_seg);
-  int rc = check_launch("adam_prep_seg_kernel");
-  if (rc) return rc;
-  int blocks = (int)std::min<size_t>((n + 1023) / 1024, 2048);
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adam_seg_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, step_state, seg_of_chunk,
-                     seg_scratch, beta1, beta2, eps, (float*)nullptr, 0.f);
-  return check_launch("adam_seg_kernel");
 }
 
 }  // extern "C"

@@ -292,91 +292,5 @@ int launch_bn_bwd(const float* dy, const float* y_raw, const float* y, const flo
 int launch_act_bwd(const float* dy, const float* y, float* dyr, float* colpart, float* dbias, int B, int C, int HW, int mode, float slope, int* fused,
                    hipStream_t s);
 int launch_colsum_finalize(const float* colpart, float* out, int B, int C, hipStream_t s);
-// element pass of the segmented Adam step (elementwise.hip: adam_seg_kernel), behind a prep kernel the caller has launched
-int launch_adam_seg(float* p, const float* g, float* m, float* v, size_t n, const int32_t* step_state, const int32_t* seg_of_chunk,
-                    const float* seg_scratch, float beta1, float beta2, float eps, hipStream_t s);
-// ... and its EMA instance (adam_seg_kernel<true>): ema' = fma(om, p' - ema, ema) for every element the pass updates, om = 1 - decay
-int launch_adam_seg_ema(float* p, const float* g, float* m, float* v, size_t n, const int32_t* step_state, const int32_t* seg_of_chunk,
-                        const float* seg_scratch, float beta1, float beta2, float eps, float* ema, float om, hipStream_t s);
-// the four prep kernels on their own, one launch each, for ms_adam_step_segmented_ema (ema.hip): elementwise.hip (lr by value),
-// lr_device.hip (lr word), loss_scale.hip (loss scale), lr_device.hip (both).  No argument checks: the caller has made them
-int launch_adam_prep_seg(int32_t* step_state, const float* norm, float max_norm, float lr, float beta1, float beta2,
-                         const int32_t* seg_first, float* seg_scratch, int n_seg, hipStream_t s);
-int launch_adam_prep_seg_lr(int32_t* step_state, const float* norm, float max_norm, const float* lr_dev, float beta1, float beta2,
-                            const int32_t* seg_first, float* seg_scratch, int n_seg, hipStream_t s);
-int launch_adam_prep_seg_scaled(int32_t* step_state, float* norm, float max_norm, float lr, float beta1, float beta2,
-                                const int32_t* seg_first, float* seg_scratch, int n_seg, int32_t* ls, int growth_interval,
-                                float min_scale, float max_scale, const int32_t* const* meeting_words, int n_meeting_words,
-                                hipStream_t s);
-int launch_adam_prep_seg_scaled_lr(int32_t* step_state, float* norm, float max_norm, const float* lr_dev, float beta1, float beta2,
-                                   const int32_t* seg_first, float* seg_scratch, int n_seg, int32_t* ls, int growth_interval,
-                                   float min_scale, float max_scale, const int32_t* const* meeting_words, int n_meeting_words,
-                                   hipStream_t s);
-
-// ---- device code shared by the prep kernels of the segmented Adam step: adam_prep_seg_kernel (elementwise.hip, lr by value),
-// adam_prep_seg_scaled_kernel (loss_scale.hip, lr by value, loss scale) and their twins that read lr from a device word
-// (lr_device.hip).  One definition of each formula: the kernels give the same bits for the same inputs.
-// (lr / bias correction 1, in fp64 and rounded once) of a segment at its step count t >= 1 ...
-__device__ inline float adam_seg_step_size(float lr, float beta1, double t) { return (float)((double)lr / (1.0 - pow((double)beta1, t))); }
-// ... and sqrt(bias correction 2)
-__device__ inline float adam_seg_bc2(float beta2, double t) { return (float)sqrt(1.0 - pow((double)beta2, t)); }
-// clip_grad_norm_'s coefficient for the true gradient norm n
-__device__ inline float adam_clip_coef(float max_norm, float n) {
-  const float coef = max_norm / (n + 1e-6f);
-  return coef > 1.f ? 1.f : coef;
-}
-__device__ inline bool adam_norm_finite(float n) { return fabsf(n) <= 3.0e38f; }
-// a learning-rate word no step may be taken with: NaN, infinite, negative or zero (lr_device.hip)
-__device__ inline bool adam_lr_bad(float lr) { return !(lr > 0.f && lr <= 3.0e38f); }
-// health words of step_state: [2] = the step is refused (adam_seg_kernel returns on it), [3] counts refused steps
-__device__ inline void adam_flag_step(int32_t* state, bool bad) {
-  state[2] = bad ? 1 : 0;
-  if (bad) state[3] += 1;
-}
-// loss scaling: did an in-launch meeting behind this step raise its error word?  Scanned by the whole workgroup and only when the
-// step is not finite; the caller combines the result over the workgroup (__syncthreads_or)
-__device__ inline int adam_meeting_raised(bool finite, const int32_t* const* __restrict__ meeting_words, int n_meeting_words) {
-  int raised = 0;
-  if (!finite)
-    for (int i = threadIdx.x; i < n_meeting_words; i += blockDim.x)
-      if (meeting_words[i] && meeting_words[i][0] != 0) raised = 1;
-  return raised;
-}
-// loss scaling: thread 0's tail of the prep kernel.  state words of `ls` (include/mixstage.h): [0] S, [1] 1/S, [2] consecutive
-// finite steps since S last changed, [3] overflow skips, [4] the last step was an overflow skip.  S moves by factors of 2 only:
-// every rescaling below is exact.  raw: norm of the SCALED gradients; bad_lr: the learning-rate word cannot be used (false where
-// lr is a kernel argument) -- a bad step whatever the gradients are, and not the scale's doing: S and its counters stay
-__device__ inline void adam_scaled_tail(int32_t* state, float* norm, float raw, bool finite, bool meeting, bool bad_lr, int step,
-                                        float max_norm, int32_t* ls, int growth_interval, float min_scale, float max_scale) {
-  float* lf = reinterpret_cast<float*>(ls);
-  float S = lf[0];
-  const float inv_S = lf[1];
-  int good = ls[2];
-  state[0] = step;
-  const float n = raw * inv_S;
-  norm[0] = n;                                     // the caller reads the true norm
-  reinterpret_cast<float*>(state)[1] = adam_clip_coef(max_norm, n) * inv_S;
-  int skipped = 0;
-  if (bad_lr) {
-    state[2] = 1;
-    state[3] += 1;
-  } else if (finite) {
-    state[2] = 0;
-    if (good < 0x7fffffff) good += 1;
-    if (growth_interval > 0 && good >= growth_interval && S < max_scale) { S *= 2.f; good = 0; }
-  } else {
-    // the update is skipped either way (adam_seg_kernel returns on word 2).  Above the floor it is the scale's doing -- halve it
-    // and try again, normal operation; AT the floor, or behind a meeting that timed out, the gradients themselves are not finite: a
-    // bad step, counted in word 3 as the unscaled path counts it
-    state[2] = 1;
-    good = 0;
-    if (S > min_scale && !meeting) { S *= 0.5f; ls[3] += 1; skipped = 1; }
-    else state[3] += 1;
-  }
-  lf[0] = S;
-  lf[1] = 1.f / S;                                 // (a power of two: exact)
-  ls[2] = good;
-  ls[4] = skipped;
-}
 
 }  // namespace ms

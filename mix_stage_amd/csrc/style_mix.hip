@@ -5,8 +5,8 @@
 // fp32, from zero, ascending s, one fma per term: a one-hot row returns the embedding row bit for bit, and nothing depends on
 // the grid.  w is addressed as w[b*w_sb + t*w_st + s] (w_st = 0: one row per clip, the training branch's softmax of the style
 // encoder's (B,S) scores); rows are used as given, not normalised.  The backward sums in fixed order, without atomics.
-// The launches run under the id twin's labels: one call of a launcher here stands for one call of its twin (as lr_device.hip
-// does for the Adam prep).
+// The launches run under the id twin's labels: one call of a launcher here stands for one call of its twin (as the lr-word forms
+// of adam.hip do for the Adam prep).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -1,5 +1,5 @@
 """Dynamic loss scaling for fp16 training: the configuration the trainer accepts and a pure-Python mirror of the rule the device
-applies (csrc/loss_scale.hip: adam_prep_seg_scaled_kernel; include/mixstage.h: ms_adam_step_segmented_scaled).
+applies (csrc/adam.hip: adam_prep_seg_kernel<true, *>, adam_scaled_tail; include/mixstage.h: ms_adam_step_segmented_scaled).
 
 The scale S multiplies the backward seed, so every activation gradient of the step is S times the true one -- out of fp16's
 subnormal range -- and the optimizer's clip coefficient carries 1/S back.  S is a power of two and moves by factors of 2 only:

@@ -1554,60 +1554,6 @@ def adam_step(p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, step_state):
                            eps, _ptr(step_state), _stream()), 'ms_adam_step')
 
 
-def adam_step_segmented(p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, step_state, seg_of_chunk, seg_first, seg_scratch):
-  check(lib().ms_adam_step_segmented(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(norm), max_norm, lr, beta1, beta2,
-                                     eps, _ptr(step_state), _ptr(seg_of_chunk), _ptr(seg_first), _ptr(seg_scratch),
-                                     seg_first.numel(), _stream()), 'ms_adam_step_segmented')
-
-
-def adam_step_segmented_scaled(p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, step_state, seg_of_chunk, seg_first, seg_scratch,
-                               loss_scale_state, growth_interval, min_scale, max_scale, meeting_table=None):
-  """adam_step_segmented on gradients that carry the loss scale S = loss_scale_state word 0 (8 int32 words on the device,
-  include/mixstage.h): `norm` holds the norm of the scaled gradients on entry and the true norm on return; the scale moves.
-  meeting_table: int64 device tensor of addresses of in-launch-meeting error words (0: unused entry), see meeting_table()."""
-  if meeting_table is not None and (meeting_table.dtype != torch.int64 or not meeting_table.is_cuda):
-    raise TypeError('adam_step_segmented_scaled: meeting_table is an int64 device tensor of addresses')
-  if loss_scale_state.dtype != torch.int32 or loss_scale_state.numel() != 8 or not loss_scale_state.is_cuda:
-    raise TypeError('adam_step_segmented_scaled: loss_scale_state is 8 int32 words on the device')
-  check(lib().ms_adam_step_segmented_scaled(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(norm), max_norm, lr, beta1, beta2,
-                                            eps, _ptr(step_state), _ptr(seg_of_chunk), _ptr(seg_first), _ptr(seg_scratch),
-                                            seg_first.numel(), _ptr(loss_scale_state), int(growth_interval), float(min_scale),
-                                            float(max_scale), _ptr(meeting_table) if meeting_table is not None else None,
-                                            meeting_table.numel() if meeting_table is not None else 0, _stream()),
-        'ms_adam_step_segmented_scaled')
-
-
-def _check_lr_word(lr_word, who):
-  if not (torch.is_tensor(lr_word) and lr_word.is_cuda and lr_word.dtype == torch.float32 and lr_word.numel() == 1):
-    raise TypeError('%s: lr_word is one fp32 word on the device' % who)
-
-
-def adam_step_segmented_lr(p, g, m, v, norm, max_norm, lr_word, beta1, beta2, eps, step_state, seg_of_chunk, seg_first, seg_scratch):
-  """adam_step_segmented with the learning rate read from `lr_word` (1-element fp32 device tensor) when the prep kernel runs: a
-  captured step follows the word from replay to replay.  Same bits as adam_step_segmented for the same lr."""
-  _check_lr_word(lr_word, 'adam_step_segmented_lr')
-  check(lib().ms_adam_step_segmented_lr(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(norm), max_norm, _ptr(lr_word), beta1,
-                                        beta2, eps, _ptr(step_state), _ptr(seg_of_chunk), _ptr(seg_first), _ptr(seg_scratch),
-                                        seg_first.numel(), _stream()), 'ms_adam_step_segmented_lr')
-
-
-def adam_step_segmented_scaled_lr(p, g, m, v, norm, max_norm, lr_word, beta1, beta2, eps, step_state, seg_of_chunk, seg_first,
-                                  seg_scratch, loss_scale_state, growth_interval, min_scale, max_scale, meeting_table=None):
-  """adam_step_segmented_scaled with the learning rate read from `lr_word`, see adam_step_segmented_lr."""
-  _check_lr_word(lr_word, 'adam_step_segmented_scaled_lr')
-  if meeting_table is not None and (meeting_table.dtype != torch.int64 or not meeting_table.is_cuda):
-    raise TypeError('adam_step_segmented_scaled_lr: meeting_table is an int64 device tensor of addresses')
-  if loss_scale_state.dtype != torch.int32 or loss_scale_state.numel() != 8 or not loss_scale_state.is_cuda:
-    raise TypeError('adam_step_segmented_scaled_lr: loss_scale_state is 8 int32 words on the device')
-  check(lib().ms_adam_step_segmented_scaled_lr(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(norm), max_norm, _ptr(lr_word),
-                                               beta1, beta2, eps, _ptr(step_state), _ptr(seg_of_chunk), _ptr(seg_first),
-                                               _ptr(seg_scratch), seg_first.numel(), _ptr(loss_scale_state), int(growth_interval),
-                                               float(min_scale), float(max_scale),
-                                               _ptr(meeting_table) if meeting_table is not None else None,
-                                               meeting_table.numel() if meeting_table is not None else 0, _stream()),
-        'ms_adam_step_segmented_scaled_lr')
-
-
 def check_ema_decay(decay, who):
   """The decay of a weight average as a float in [0, 1); ValueError otherwise (NaN, infinite, negative, 1 or more)."""
   try:
@@ -1619,6 +1565,77 @@ def check_ema_decay(decay, who):
   return d
 
 
+def _adam_segmented(who, p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, step_state, seg_of_chunk, seg_first, seg_scratch,
+                    lr_word=None, loss_scale=None, ema=None):
+  """The segmented Adam step behind every public wrapper below (`who`, named by the exceptions).  The form is what is given:
+  lr_word -- the 1-element fp32 device tensor the prep kernel reads lr from (`lr` is then ignored); loss_scale -- (loss_scale_state,
+  growth_interval, min_scale, max_scale, meeting_table); ema -- (ema, ema_decay).  Each form without `ema` has a C entry point of
+  its own; ms_adam_step_segmented_ema takes all four (a NULL word / NULL loss_scale_state: lr by value / unscaled)."""
+  if ema is not None:
+    avg, decay = ema
+    if not (torch.is_tensor(avg) and avg.is_cuda and avg.dtype == torch.float32 and avg.is_contiguous() and avg.numel() == p.numel()):
+      raise TypeError('%s: ema is a contiguous fp32 device tensor with as many elements as p' % who)
+    decay = check_ema_decay(decay, who)
+  if lr_word is not None and not (torch.is_tensor(lr_word) and lr_word.is_cuda and lr_word.dtype == torch.float32
+                                  and lr_word.numel() == 1):
+    raise TypeError('%s: lr_word is one fp32 word on the device' % who)
+  scale = ()
+  if loss_scale is not None:
+    ls_state, growth_interval, min_scale, max_scale, table = loss_scale
+    if table is not None and (table.dtype != torch.int64 or not table.is_cuda):
+      raise TypeError('%s: meeting_table is an int64 device tensor of addresses' % who)
+    if ls_state is not None or ema is None:          # (adam_step_segmented_ema without a state: its unscaled form, the rest is unused)
+      if ls_state.dtype != torch.int32 or ls_state.numel() != 8 or not ls_state.is_cuda:
+        raise TypeError('%s: loss_scale_state is 8 int32 words on the device' % who)
+      scale = (_ptr(ls_state), int(growth_interval), float(min_scale), float(max_scale), _ptr(table) if table is not None else None,
+               table.numel() if table is not None else 0)
+  head = (_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(norm), max_norm)
+  tail = (beta1, beta2, eps, _ptr(step_state), _ptr(seg_of_chunk), _ptr(seg_first), _ptr(seg_scratch), seg_first.numel())
+  if ema is not None:
+    sym = 'ms_adam_step_segmented_ema'
+    args = head + (0.0 if lr is None else float(lr), _ptr(lr_word) if lr_word is not None else None) + tail \
+        + (scale or (None, 0, 1.0, 1.0, None, 0)) + (_ptr(avg), decay)
+  else:
+    sym = 'ms_adam_step_segmented' + ('_scaled' if scale else '') + ('_lr' if lr_word is not None else '')
+    args = head + (_ptr(lr_word) if lr_word is not None else lr,) + tail + scale
+  check(getattr(lib(), sym)(*args, _stream()), sym)
+
+
+def adam_step_segmented(p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, step_state, seg_of_chunk, seg_first, seg_scratch):
+  _adam_segmented('adam_step_segmented', p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, step_state, seg_of_chunk, seg_first,
+                  seg_scratch)
+
+
+def adam_step_segmented_scaled(p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, step_state, seg_of_chunk, seg_first, seg_scratch,
+                               loss_scale_state, growth_interval, min_scale, max_scale, meeting_table=None):
+  """adam_step_segmented on gradients that carry the loss scale S = loss_scale_state word 0 (8 int32 words on the device,
+  include/mixstage.h): `norm` holds the norm of the scaled gradients on entry and the true norm on return; the scale moves.
+  meeting_table: int64 device tensor of addresses of in-launch-meeting error words (0: unused entry), see meeting_table()."""
+  _adam_segmented('adam_step_segmented_scaled', p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, step_state, seg_of_chunk,
+                  seg_first, seg_scratch, loss_scale=(loss_scale_state, growth_interval, min_scale, max_scale, meeting_table))
+
+
+def _lr_word(lr_word, who):
+  if lr_word is None:                                # (to _adam_segmented, None is "lr by value")
+    raise TypeError('%s: lr_word is one fp32 word on the device' % who)
+  return lr_word
+
+
+def adam_step_segmented_lr(p, g, m, v, norm, max_norm, lr_word, beta1, beta2, eps, step_state, seg_of_chunk, seg_first, seg_scratch):
+  """adam_step_segmented with the learning rate read from `lr_word` (1-element fp32 device tensor) when the prep kernel runs: a
+  captured step follows the word from replay to replay.  Same bits as adam_step_segmented for the same lr."""
+  _adam_segmented('adam_step_segmented_lr', p, g, m, v, norm, max_norm, None, beta1, beta2, eps, step_state, seg_of_chunk, seg_first,
+                  seg_scratch, lr_word=_lr_word(lr_word, 'adam_step_segmented_lr'))
+
+
+def adam_step_segmented_scaled_lr(p, g, m, v, norm, max_norm, lr_word, beta1, beta2, eps, step_state, seg_of_chunk, seg_first,
+                                  seg_scratch, loss_scale_state, growth_interval, min_scale, max_scale, meeting_table=None):
+  """adam_step_segmented_scaled with the learning rate read from `lr_word`, see adam_step_segmented_lr."""
+  _adam_segmented('adam_step_segmented_scaled_lr', p, g, m, v, norm, max_norm, None, beta1, beta2, eps, step_state, seg_of_chunk,
+                  seg_first, seg_scratch, lr_word=_lr_word(lr_word, 'adam_step_segmented_scaled_lr'),
+                  loss_scale=(loss_scale_state, growth_interval, min_scale, max_scale, meeting_table))
+
+
 def adam_step_segmented_ema(p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, step_state, seg_of_chunk, seg_first, seg_scratch,
                             ema, ema_decay, lr_word=None, loss_scale_state=None, growth_interval=0, min_scale=1.0, max_scale=1.0,
                             meeting_table=None):
@@ -1626,25 +1643,9 @@ def adam_step_segmented_ema(p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, s
   ignored); unscaled, or with the loss scale of `loss_scale_state` when it is given -- that also moves `ema`, an fp32 device
   tensor with the layout of `p`, inside the element pass: ema += (1 - ema_decay) * (p_new - ema) for every element the step
   updates (include/mixstage.h: ms_adam_step_segmented_ema).  p, m, v and the state words get the bits of the form without it."""
-  if not (torch.is_tensor(ema) and ema.is_cuda and ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() == p.numel()):
-    raise TypeError('adam_step_segmented_ema: ema is a contiguous fp32 device tensor with as many elements as p')
-  d = check_ema_decay(ema_decay, 'adam_step_segmented_ema')
-  if lr_word is not None:
-    _check_lr_word(lr_word, 'adam_step_segmented_ema')
-  if meeting_table is not None and (meeting_table.dtype != torch.int64 or not meeting_table.is_cuda):
-    raise TypeError('adam_step_segmented_ema: meeting_table is an int64 device tensor of addresses')
-  if loss_scale_state is not None and (loss_scale_state.dtype != torch.int32 or loss_scale_state.numel() != 8
-                                       or not loss_scale_state.is_cuda):
-    raise TypeError('adam_step_segmented_ema: loss_scale_state is 8 int32 words on the device')
-  check(lib().ms_adam_step_segmented_ema(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(norm), max_norm,
-                                         0.0 if lr is None else float(lr), _ptr(lr_word) if lr_word is not None else None,
-                                         beta1, beta2, eps, _ptr(step_state), _ptr(seg_of_chunk), _ptr(seg_first),
-                                         _ptr(seg_scratch), seg_first.numel(),
-                                         _ptr(loss_scale_state) if loss_scale_state is not None else None, int(growth_interval),
-                                         float(min_scale), float(max_scale),
-                                         _ptr(meeting_table) if meeting_table is not None else None,
-                                         meeting_table.numel() if meeting_table is not None else 0, _ptr(ema), d, _stream()),
-        'ms_adam_step_segmented_ema')
+  _adam_segmented('adam_step_segmented_ema', p, g, m, v, norm, max_norm, lr, beta1, beta2, eps, step_state, seg_of_chunk, seg_first,
+                  seg_scratch, lr_word=lr_word, loss_scale=(loss_scale_state, growth_interval, min_scale, max_scale, meeting_table),
+                  ema=(ema, ema_decay))
 
 
 def write_floats(dst, values):

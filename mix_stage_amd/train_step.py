@@ -332,29 +332,16 @@ class FlatAdam:
     """total_norm = ||g||_2 over all parameters; g *= min(1, max_norm/(norm+1e-6)); Adam update (per-parameter step
     counts).  count=False while a HIP graph is being captured (nothing executes)."""
     ops.grad_norm(self.flat_g, self.norm, self.partials)
-    # device_lr: the same launches with lr read from the device word (same bits for the same lr)
-    lr = self.lr_word if self.device_lr else self.lr
-    if self.ema is not None:
-      # one entry point for the four forms below: the same prep launch, the element pass also moves the average
-      rule = self.loss_scale
-      ops.adam_step_segmented_ema(
-          self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm, self.max_norm, None if self.device_lr else self.lr,
-          self.betas[0], self.betas[1], self.eps, self.step_state, self.seg_of_chunk, self.seg_first, self.seg_scratch,
-          self.ema, self.ema_decay, lr_word=self.lr_word, loss_scale_state=self.ls_state if rule is not None else None,
-          growth_interval=rule.growth_interval if rule is not None else 0, min_scale=rule.min if rule is not None else 1.0,
-          max_scale=rule.max if rule is not None else 1.0, meeting_table=self.meeting_table if rule is not None else None)
-    elif self.loss_scale is None:
-      (ops.adam_step_segmented_lr if self.device_lr else ops.adam_step_segmented)(
-          self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm, self.max_norm, lr,
-          self.betas[0], self.betas[1], self.eps, self.step_state, self.seg_of_chunk, self.seg_first,
-          self.seg_scratch)
-    else:
-      # flat_g and norm hold S x the gradients / their norm: un-scaled inside the prep launch (norm in place), S moves there
-      rule = self.loss_scale
-      (ops.adam_step_segmented_scaled_lr if self.device_lr else ops.adam_step_segmented_scaled)(
-          self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm, self.max_norm, lr,
-          self.betas[0], self.betas[1], self.eps, self.step_state, self.seg_of_chunk, self.seg_first,
-          self.seg_scratch, self.ls_state, rule.growth_interval, rule.min, rule.max, self.meeting_table)
+    # One call, two launches, whatever is configured (ops._adam_segmented picks the entry point of the form).  device_lr: lr is read
+    # from the device word (same bits for the same lr).  loss_scale: flat_g and norm hold S x the gradients / their norm, un-scaled
+    # inside the prep launch (norm in place), S moves there.  ema: the element pass also moves the average
+    rule = self.loss_scale
+    ops._adam_segmented(
+        'FlatAdam.clip_and_step', self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.norm, self.max_norm,
+        None if self.device_lr else self.lr, self.betas[0], self.betas[1], self.eps, self.step_state, self.seg_of_chunk,
+        self.seg_first, self.seg_scratch, lr_word=self.lr_word if self.device_lr else None,
+        loss_scale=None if rule is None else (self.ls_state, rule.growth_interval, rule.min, rule.max, self.meeting_table),
+        ema=None if self.ema is None else (self.ema, self.ema_decay))
     ops.refresh_prepared_weights(self.flat_p)        # data-gradient weights of all blocks of this network: one launch
     self.seen_version = self._param_versions()
     if count:

@@ -12,7 +12,7 @@ One entry per case, in the style of dispatch_table.py:
            of torch's float32 CPU evaluation of the same formula against the float64 reference, floored at 2 * 2^-24)
   claims   the branch of the launcher / kernel the case exists for, as numbers that tests/test_ew_table_cpu.py recomputes from
            the mirrors below (which it ties to the constants in the sources by regex)
-  why      the same in words, with file:line of csrc/elementwise.hip (E:) or csrc/elementwise16.hip (E16:)
+  why      the same in words, with file:line of csrc/elementwise.hip (E:), csrc/elementwise16.hip (E16:) or csrc/adam.hip (A:)
   p        the shape parameters of the runner
 
 The mirrors restate the launchers' grid arithmetic; the CPU guard fails if a constant they use changes in the sources."""
@@ -21,8 +21,8 @@ RED_MAX_BLOCKS = 1024          # E:1175
 RED_PER_BLOCK = 256 * 8        # E:1409 red_blocks
 MIX_TT = 64                    # E:729
 MIX_WG_TARGET = 512            # E:1582
-EW_BLOCK_CAP = 2048            # E:1675 znorm, E:1720 / E:1732 concat, E:1970 / E:1985 Adam
-ADAM_PER_BLOCK = 1024          # E:1970
+EW_BLOCK_CAP = 2048            # E:1675 znorm, E:1720 / E:1732 concat, A:298 Adam
+ADAM_PER_BLOCK = 1024          # A:298
 CE_REG_MAX = 8                 # E:1069 `C <= 8`
 LP_PAIR_MAX = 2048             # E:1856
 BN_GY_MAX = 64                 # E:1653
@@ -158,20 +158,20 @@ _ADAM_BIG = 2 * 2048 * 1024 + 64 * 1000
 for _id, _n, _seg, _norms, _offset, _why in [
     ('n64_one', 64, 'one', ('in', 'clip', 'in'), True, 'one chunk, one segment: 16 vectors, most threads idle'),
     ('n64000_chunks', 64000, 'chunks', ('clip', 'in', 'clip'), True,
-     'a segment boundary at every chunk; segments never updated (-1: p, m, v bit-unchanged, E:1379) and starting in the future (E:1317); per-segment t = step - first + 1 (E:1318)'),
+     'a segment boundary at every chunk; segments never updated (-1: p, m, v bit-unchanged, A:258) and starting in the future (A:172); per-segment t = step - first + 1 (A:173)'),
     ('big_uneven', _ADAM_BIG, 'uneven', ('in', 'clip', 'clip'), True,
-     'above 2 * 2048 * 1024 elements: capped grid, the two-vector loop runs more than once per thread and the second vector of the last pass is partly off the end (E:1369-1376)'),
+     'above 2 * 2048 * 1024 elements: capped grid, the two-vector loop runs more than once per thread and the second vector of the last pass is partly off the end (A:248-259)'),
     ('n64000_nonfinite', 64000, 'chunks', ('in', 'inf', 'nan', 'clip'), False,
-     'norm = inf, then nan: p, m, v bit-unchanged, step_state[2] == 1, step_state[3] counts, the clock advances: the 4th step uses t = 4 (E:1336-1338)'),
+     'norm = inf, then nan: p, m, v bit-unchanged, step_state[2] == 1, step_state[3] counts, the clock advances: the 4th step uses t = 4 (A:202-204)'),
 ]:
   _case('adam_seg_' + _id, 'adam', ('ew|ew_adam_step_segmented',), ('ms_adam_step_segmented',), 'ops.adam_step_segmented', 'derived',
-        _why + ('; the same steps on views offset by one float (scalar fallback E:1397) equal the aligned ones bit for bit' if _offset else ''),
+        _why + ('; the same steps on views offset by one float (scalar fallback A:283) equal the aligned ones bit for bit' if _offset else ''),
         claims=dict(blocks=adam_blocks(_n), capped=_n > EW_BLOCK_CAP * ADAM_PER_BLOCK, two_passes=_n > 2 * EW_BLOCK_CAP * ADAM_PER_BLOCK),
         n=_n, seg=_seg, norms=_norms, offset=_offset, segmented=True)
 for _id, _n, _norms, _why in [
-    ('n64001', 64001, ('clip', 'in', 'in'), 'the unsegmented step (E:1292), n not a multiple of 4'),
+    ('n64001', 64001, ('clip', 'in', 'in'), 'the unsegmented step (A:45), n not a multiple of 4'),
     ('big', _ADAM_BIG, ('in', 'clip', 'in'), 'the unsegmented step on the capped grid: grid-stride loop over 2048 blocks'),
-    ('nonorm', 1000, ('none', 'none', 'none'), 'norm = NULL: no clipping (E:1280)'),
+    ('nonorm', 1000, ('none', 'none', 'none'), 'norm = NULL: no clipping (A:33)'),
 ]:
   _case('adam_plain_' + _id, 'adam', ('ew|ew_adam_step',), ('ms_adam_step',), 'ops.adam_step', 'derived', _why,
         claims=dict(blocks=adam_blocks(_n), capped=_n > EW_BLOCK_CAP * ADAM_PER_BLOCK, two_passes=_n > 2 * EW_BLOCK_CAP * ADAM_PER_BLOCK),

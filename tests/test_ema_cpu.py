@@ -79,11 +79,11 @@ def test_header_declares_the_entry_point_with_the_arguments_signatures_lists():
 
 def test_the_sources_keep_the_new_entry_point_out_of_the_elementwise_files():
   csrc = os.path.join(ROOT, 'mix_stage_amd', 'csrc')
-  ema = open(os.path.join(csrc, 'ema.hip')).read()
-  assert 'int ms_adam_step_segmented_ema(' in ema and '"ew|ew_adam_step_segmented"' in ema
+  adam = open(os.path.join(csrc, 'adam.hip')).read()
+  assert 'int ms_adam_step_segmented_ema(' in adam and '"ew|ew_adam_step_segmented"' in adam
   for fn in ('elementwise.hip', 'elementwise16.hip'):
     assert 'ms_adam_step_segmented_ema' not in open(os.path.join(csrc, fn)).read()
-  assert 'ema.hip' in open(os.path.join(csrc, 'Makefile')).read()
+  assert 'adam.hip' in open(os.path.join(csrc, 'Makefile')).read()
 
 
 @pytest.mark.parametrize('bad', BAD_DECAYS, ids=[repr(b) for b in BAD_DECAYS])

@@ -13,7 +13,15 @@ from helpers.dispatch_table import EXCLUDED
 from test_dispatch_table_cpu import CSRC, timing_formats
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EW_SOURCES = ('elementwise.hip', 'elementwise16.hip')
+EW_SOURCES = ('elementwise.hip', 'elementwise16.hip', 'adam.hip')
+# entry points of adam.hip that the table does not call: the forms of the segmented step with a feature, each exercised against its
+# twin by a GPU test file of its own -> (that file, the ops wrapper it has to call)
+ADAM_FORMS = {
+    'ms_adam_step_segmented_scaled': ('test_gpu_loss_scale.py', 'ops.adam_step_segmented_scaled'),
+    'ms_adam_step_segmented_lr': ('test_gpu_lr_schedule.py', 'ops.adam_step_segmented_lr'),
+    'ms_adam_step_segmented_scaled_lr': ('test_gpu_lr_schedule.py', 'ops.adam_step_segmented_scaled_lr'),
+    'ms_adam_step_segmented_ema': ('test_gpu_ema.py', 'ops.adam_step_segmented_ema'),
+}
 
 # every case of the table by name: a case that is removed or renamed fails here (a new case is added to this list with it)
 CASE_IDS = '''
@@ -98,7 +106,12 @@ def test_every_ew_entry_point_is_called_by_a_case():
   called = set()
   for e in T.TABLE:
     called.update(e['symbols'])
-  missing = sorted(s for s in syms if s not in called)
+  assert set(ADAM_FORMS) <= set(syms), sorted(syms)
+  for sym, (test, wrapper) in ADAM_FORMS.items():
+    path = os.path.join(ROOT, 'tests', test)
+    assert syms[sym] == 'adam.hip' and os.path.exists(path), (sym, test)
+    assert re.search(r'\b%s\b\s*[()]' % re.escape(wrapper), open(path).read()), '%s does not call %s' % (test, wrapper)
+  missing = sorted(s for s in syms if s not in called and s not in ADAM_FORMS)
   assert not missing, 'C-ABI entry points behind an ew| TimingScope that no case calls: %s' % missing
   header = open(os.path.join(ROOT, 'include', 'mixstage.h')).read()
   unknown = sorted(s for s in called if not re.search(r'\b%s\s*\(' % s, header))
@@ -125,17 +138,19 @@ def test_mirror_constants_are_the_ones_in_the_sources():
   for fn, rx in (('ms_znorm_select', r'\(rows \* PK \+ 255\) / 256, (\d+)\)'), ('ms_concat_style_fwd', r'\(total \+ 255\) / 256, (\d+)\)'),
                  ('ms_concat_style_bwd', r'\(total \+ 255\) / 256, (\d+)\)')):
     assert one(rx, fns[fn]) == T.EW_BLOCK_CAP, fn
-  for fn in ('ms_adam_step', 'ms_adam_step_segmented'):
-    m = re.search(r'\(n \+ (\d+)\) / (\d+), (\d+)\)', fns[fn])
-    assert m and int(m.group(1)) + 1 == int(m.group(2)) == T.ADAM_PER_BLOCK and int(m.group(3)) == T.EW_BLOCK_CAP, fn
+  adam = _src('adam.hip')
+  m = re.findall(r'\(n \+ (\d+)\) / (\d+), (\d+)\)', adam)          # the one grid of both element passes
+  assert len(m) == 1 and m == re.findall(r'\(n \+ (\d+)\) / (\d+), (\d+)\)', _functions(adam)['adam_blocks']), m
+  assert int(m[0][0]) + 1 == int(m[0][1]) == T.ADAM_PER_BLOCK and int(m[0][2]) == T.EW_BLOCK_CAP
   assert s.count('if (C <= 8)') == 1 and T.CE_REG_MAX == 8
   for fn in ('ms_lp_mean_pair_fwd', 'ms_lp_mean_pair_bwd'):
     assert one(r'n > (\d+)\)', fns[fn]) == T.LP_PAIR_MAX, fn
   assert re.search(r'std::min\(64, \(B \* HW \+ 2047\) / 2048\)', fns['ms_bn_bwd_apply']) and T.BN_GY_MAX == 64
   assert re.search(r'C >= 1024 \? 1 : \(1024 \+ C - 1\) / C', fns['bwd_chunks'])
   assert one(r'COPY_MULTI_MAX = (\d+)') == T.COPY_MULTI_MAX
-  # the unsegmented / segmented Adam and the norm kernel: the alignment tests the offset-by-one-float cases rely on
+  # the norm kernel and the segmented Adam's element pass: the alignment tests the offset-by-one-float cases rely on
   assert s.count('& 15) == 0') >= 3
+  assert '((size_t)p | (size_t)g | (size_t)m | (size_t)v | (EMA ? (size_t)e : (size_t)0)) & 15) == 0' in adam
 
 
 def test_mirrors_against_hand_computed_values():

@@ -283,6 +283,52 @@ def test_a_null_lr_word_is_an_error_and_launches_nothing():
                                fl.seg_of_chunk, fl.seg_first, fl.seg_scratch)
 
 
+def test_without_a_norm_lr_by_value_leaves_the_health_words_and_the_lr_word_form_writes_them():
+  """norm = NULL at the C ABI (no clipping: the coefficient is 1), from preset health words [2] = a, [3] = 7.  With lr by value the
+  prep kernel does not write words 2 and 3 at all -- a flag that is set stays set and the element pass returns on it; with lr from
+  the word it always writes them, from the word alone."""
+  from mix_stage_amd import ops
+  L = ops.lib()
+  P = lambda t: ctypes.c_void_p(t.data_ptr())
+  stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+  g = _grads(SMALL, 1)[0]
+  sizes, first = SMALL
+  act = (torch.tensor(first).repeat_interleave(torch.tensor(sizes)) == 1).to(DEV)      # step 1: -1 never starts, 2 is still ahead
+
+  def run(a, lr=None, word=None, norm=None):
+    fl = _Flat(SMALL)
+    fl.g.copy_(g)
+    fl.step_state.copy_(torch.tensor([0, 0, a, 7], dtype=torch.int32))
+    before = [t.clone() for t in (fl.p, fl.m, fl.v)]
+    if norm is not None:
+      fl.norm.fill_(norm)
+    head = (P(fl.p), P(fl.g), P(fl.m), P(fl.v), fl.n, P(fl.norm) if norm is not None else None, MAX_NORM)
+    tail = (BETAS[0], BETAS[1], EPS, P(fl.step_state), P(fl.seg_of_chunk), P(fl.seg_first), P(fl.seg_scratch), len(sizes))
+    if word is None:
+      assert L.ms_adam_step_segmented(*head, lr, *tail, stream) == 0
+    else:
+      assert L.ms_adam_step_segmented_lr(*head, P(fl.lr_word.fill_(word)), *tail, stream) == 0
+    torch.cuda.synchronize()
+    state = fl.step_state.tolist()
+    assert state[0] == 1 and float(fl.step_state.view(torch.float32)[1]) == 1.0          # the clock advanced, nothing is clipped
+    moved = not torch.equal(fl.p, before[0])
+    if not moved:
+      assert all(torch.equal(x, y) for x, y in zip(before, (fl.p, fl.m, fl.v)))
+    else:
+      assert bool((fl.p != before[0])[act].any()) and torch.equal(fl.p[~act], before[0][~act])
+    return fl, state[2:], moved
+
+  fl, words, moved = run(0, lr=1e-4)
+  assert words == [0, 7] and moved
+  ref, ref_words, _ = run(0, lr=1e-4, norm=1e-30)       # a norm so small that the coefficient clamps to 1: the same step
+  assert ref_words == [0, 7]
+  for name in ('p', 'm', 'v', 'seg_scratch'):
+    assert torch.equal(fl.words()[name], ref.words()[name]), name
+  assert run(1, lr=1e-4)[1:] == ([1, 7], False)
+  assert run(1, word=1e-4)[1:] == ([0, 7], True)
+  assert run(0, word=0.0)[1:] == ([1, 8], False)
+
+
 # ------------------------------------------------------------------------------------------------ trainer level
 M_ = S_ = 2
 GAMMA = 0.5

@@ -1,5 +1,5 @@
 """CPU: the loss-scale rule of fp16 training -- the pure-Python mirror (mix_stage_amd/loss_scale.py) of what the device applies
-(csrc/loss_scale.hip), against hand-written sequences: growth at the interval, the cap at max, halving, the floor turning a skip into
+(csrc/adam.hip), against hand-written sequences: growth at the interval, the cap at max, halving, the floor turning a skip into
 a bad step, the static form; and the configurations the trainer accepts or rejects.  tests/test_gpu_loss_scale.py holds the device
 to the same mirror word for word."""
 import os
