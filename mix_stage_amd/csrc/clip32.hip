@@ -21,6 +21,7 @@
 
 #include "kernels.h"
 #include "conv16.h"
+#include "job_queue.h"
 
 namespace ms {
 
@@ -678,10 +679,9 @@ struct ClipPrepBatch { int n; ClipPrepJob job[CLIP_PREP_MAX]; };
 constexpr int CLP_LDS = 32 * 289;
 __global__ __launch_bounds__(256) void clip32_prep_kernel(const ClipPrepBatch pb) {
   __shared__ float lds[CLP_LDS];
-  int j = 0;
-  while (j + 1 < pb.n && (int)blockIdx.x >= pb.job[j].block_end) ++j;
-  const ClipPrepJob& jb = pb.job[j];
-  const int blk = blockIdx.x - (j ? pb.job[j - 1].block_end : 0);
+  const JobSlot at = find_job(pb.n, (int)blockIdx.x, [&](int k) { return pb.job[k].block_end; });
+  const ClipPrepJob& jb = pb.job[at.j];
+  const int blk = (int)blockIdx.x - at.first;
   const int wv = blk & 3, ct = blk >> 2, t = threadIdx.x;
   const int KW = jb.KW, k8w = jb.k8w;
   const int c_lo = wv * k8w * 8, nc = min(k8w * 8, max(0, jb.red - c_lo));       // reduction channels of this wave

@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "conv16_kernel.h"
+#include "job_queue.h"
 
 namespace ms {
 
@@ -295,12 +296,10 @@ __device__ inline void prep16_unit(const Prep16Job& jb, int unit, float* lds) {
 
 __global__ __launch_bounds__(256) void prep16_multi_kernel(const Prep16Batch pb) {
   __shared__ float lds[PREP16_LDS + 64];
-  int j = 0;
-  while (j + 1 < pb.n && (int)blockIdx.x >= pb.job[j].block_end) ++j;
-  const Prep16Job& jb = pb.job[j];
-  const int b0 = j ? pb.job[j - 1].block_end : 0, nb = jb.block_end - b0;
+  const JobSlot at = find_job(pb.n, (int)blockIdx.x, [&](int k) { return pb.job[k].block_end; });
+  const Prep16Job& jb = pb.job[at.j];
   const int units = prep16_units(jb);
-  for (int u = (int)blockIdx.x - b0; u < units; u += nb) {
+  for (int u = (int)blockIdx.x - at.first; u < units; u += at.count) {
     if (jb.dt == DT_BF16) prep16_unit<BF16>(jb, u, lds);
     else prep16_unit<F16>(jb, u, lds);
   }

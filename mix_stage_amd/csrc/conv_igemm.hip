@@ -10,10 +10,10 @@
 // Replaces what ATen's convolution / convolution_backward compute for the reference's
 // ConvNormRelu / nn.Conv1d calls (layers.py:58-78, JL:83, S2G:50-63).
 #include <algorithm>
-#include <mutex>
 #include <vector>
 
 #include "kernels.h"
+#include "job_queue.h"
 
 namespace ms {
 
@@ -444,10 +444,9 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs p) {
 // reads.  They wait in a queue and run side by side in one launch per kernel shape at the end of the backward pass.
 template <int KH_, int KW_, bool UP2>
 __global__ __launch_bounds__(256) void wgrad_multi_kernel(const WgradBatch b) {
-  int j = 0;
-  while (j + 1 < b.n && (int)blockIdx.x >= b.block_end[j]) ++j;
-  const WgradArgs& p = b.job[j];
-  const int id = (int)blockIdx.x - (j ? b.block_end[j - 1] : 0);
+  const JobSlot at = find_job(b.n, (int)blockIdx.x, [&](int k) { return b.block_end[k]; });
+  const WgradArgs& p = b.job[at.j];
+  const int id = (int)blockIdx.x - at.first;
   const int gx = (p.Kg + 63) / 64, gy = (p.Cog + 63) / 64;
   const int bz = id / (gx * gy), r = id - bz * gx * gy;
   wgrad_body<1, 1, KH_, KW_, UP2>(p, r % gx, r / gx, bz);
@@ -490,11 +489,9 @@ __global__ void reduce_splits_kernel(const float* __restrict__ part, float* __re
 // many blocks' split reductions in ONE launch, ACCUMULATING into out (the caller zeroes out once per step); each job keeps
 // the summation order of the single-job kernel it replaces (wave: lanes stride over the splits), so results are the same
 __global__ __launch_bounds__(256) void reduce_splits_multi_kernel(const ReduceBatch rb) {
-  int j = 0;
-  while (j + 1 < rb.n && (int)blockIdx.x >= rb.job[j].block_end) ++j;
-  const ReduceJob jb = rb.job[j];
-  const int b = (int)blockIdx.x - (j ? rb.job[j - 1].block_end : 0);
-  const int nb = jb.block_end - (j ? rb.job[j - 1].block_end : 0);
+  const JobSlot at = find_job(rb.n, (int)blockIdx.x, [&](int k) { return rb.job[k].block_end; });
+  const ReduceJob jb = rb.job[at.j];
+  const int b = (int)blockIdx.x - at.first, nb = at.count;
   if (jb.wave) {
     const int lane = threadIdx.x & 63;
     const int i = b * 4 + (threadIdx.x >> 6);
@@ -572,10 +569,8 @@ __global__ void transpose_weight_kernel(const TransposeJob jb) {
 
 // many blocks' data-gradient weights in ONE launch: job j owns workgroups [block_end[j-1], block_end[j])
 __global__ void transpose_weight_multi_kernel(const TransposeBatch tb) {
-  int j = 0;
-  while (j + 1 < tb.n && (int)blockIdx.x >= tb.job[j].block_end) ++j;
-  const int b0 = j ? tb.job[j - 1].block_end : 0;
-  transpose_weight_elems(tb.job[j], ((int)blockIdx.x - b0) * blockDim.x + threadIdx.x, (tb.job[j].block_end - b0) * blockDim.x);
+  const JobSlot at = find_job(tb.n, (int)blockIdx.x, [&](int k) { return tb.job[k].block_end; });
+  transpose_weight_elems(tb.job[at.j], ((int)blockIdx.x - at.first) * blockDim.x + threadIdx.x, at.count * blockDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -955,13 +950,9 @@ int launch_reduce_splits_multi(ReduceBatch& rb, hipStream_t s) {
 }
 
 struct PendingWgrad { WgradArgs a; int up2, nwg; double flops, bytes; };
-static std::vector<PendingWgrad> g_pending_wg;       // process-wide, like the patch kernels' queue (wgrad_patch.hip)
-static std::mutex g_pending_wg_mu;
+static PendingQueue<PendingWgrad> g_pending_wg;
 
-void wgrad_gather_discard() {
-  std::lock_guard<std::mutex> lk(g_pending_wg_mu);
-  g_pending_wg.clear();
-}
+void wgrad_gather_discard() { g_pending_wg.discard(); }
 
 template <int KH, int KW, bool UP2>
 static void launch_wgrad_multi(const WgradBatch& b, hipStream_t s) {
@@ -969,27 +960,21 @@ static void launch_wgrad_multi(const WgradBatch& b, hipStream_t s) {
 }
 
 int wgrad_gather_flush(hipStream_t s) {
-  std::vector<PendingWgrad> q;
-  {
-    std::lock_guard<std::mutex> lk(g_pending_wg_mu);
-    q.swap(g_pending_wg);
-  }
-  // one launch per kernel shape: (1 x 4), (1 x 3), (1 x 3 on an upsample-add input), everything else through the run-time shape
+  std::vector<PendingWgrad> q = g_pending_wg.take();
+  // one launch per kernel shape and per WG_MAX_JOBS jobs, shape 0 first: (1 x 4), (1 x 3), (1 x 3 on an upsample-add input),
+  // everything else through the run-time shape
   auto shape_of = [](const PendingWgrad& w) {
     if (w.a.KH == 1 && w.a.KW == 4 && !w.up2) return 0;
     if (w.a.KH == 1 && w.a.KW == 3) return w.up2 ? 2 : 1;
     return w.up2 ? 4 : 3;
   };
-  for (int shape = 0; shape < 5; ++shape) {
-    WgradBatch b;
-    b.n = 0;
-    long blocks = 0;
-    double flops = 0, bytes = 0;
-    auto launch = [&]() -> int {
-      if (!b.n) return 0;
-      TimingScope ts(s, flops, bytes, "wgrad_multi_kernel<%d>|conv_wgrad_gather multi shape%d jobs%d wgs%ld", shape, shape, b.n, blocks);
-      int rc = 0;
-      if (!ts.skip()) {
+  sort_jobs(q, shape_of);
+  return pack_jobs<WgradBatch>(
+      q, [&](const PendingWgrad& x, const PendingWgrad& h) { return shape_of(x) == shape_of(h); },
+      [&](const PendingWgrad& h, const WgradBatch& b, const std::vector<const PendingWgrad*>&, const JobTotals& t) -> int {
+        const int shape = shape_of(h);
+        TimingScope ts(s, t.flops, t.bytes, "wgrad_multi_kernel<%d>|conv_wgrad_gather multi shape%d jobs%d wgs%ld", shape, shape, b.n, t.wgs);
+        if (ts.skip()) return 0;
         switch (shape) {
           case 0: launch_wgrad_multi<1, 4, false>(b, s); break;
           case 1: launch_wgrad_multi<1, 3, false>(b, s); break;
@@ -997,24 +982,8 @@ int wgrad_gather_flush(hipStream_t s) {
           case 3: launch_wgrad_multi<0, 0, false>(b, s); break;
           default: launch_wgrad_multi<0, 0, true>(b, s); break;
         }
-        rc = check_launch("wgrad_multi_kernel");
-      }
-      b.n = 0; blocks = 0; flops = bytes = 0;
-      return rc;
-    };
-    for (const PendingWgrad& w : q) {
-      if (shape_of(w) != shape) continue;
-      if (b.n == WG_MAX_JOBS) { const int rc = launch(); if (rc) return rc; }
-      blocks += w.nwg;
-      b.block_end[b.n] = (int)blocks;
-      b.job[b.n] = w.a;
-      ++b.n;
-      flops += w.flops; bytes += w.bytes;
-    }
-    const int rc = launch();
-    if (rc) return rc;
-  }
-  return 0;
+        return check_launch("wgrad_multi_kernel");
+      });
 }
 
 // queue = true: nothing of this call reads the result (dw written in place -- ADDED to, the slot may already hold the parameter's
@@ -1037,8 +1006,7 @@ int launch_wgrad(WgradArgs a, bool up2, float* dw, float* partial_ws, bool defer
     w.up2 = up2 ? 1 : 0;
     w.nwg = (int)(grid.x * grid.y * grid.z);
     w.flops = flops; w.bytes = bytes;
-    std::lock_guard<std::mutex> lk(g_pending_wg_mu);
-    g_pending_wg.push_back(w);
+    g_pending_wg.push(w);
     return 0;
   }
   int rc;

@@ -20,6 +20,7 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "job_queue.h"
 
 namespace ms {
 
@@ -89,11 +90,8 @@ __device__ inline void split_weights_elems(const SplitJob& jb, size_t first, siz
 
 // many weight tensors in ONE launch: job j owns workgroups [block_end[j-1], block_end[j])
 __global__ void split_weights_multi_kernel(const SplitBatch sb) {
-  int j = 0;
-  while (j + 1 < sb.n && (int)blockIdx.x >= sb.job[j].block_end) ++j;
-  const int b0 = j ? sb.job[j - 1].block_end : 0;
-  split_weights_elems(sb.job[j], (size_t)((int)blockIdx.x - b0) * blockDim.x + threadIdx.x,
-                      (size_t)(sb.job[j].block_end - b0) * blockDim.x);
+  const JobSlot at = find_job(sb.n, (int)blockIdx.x, [&](int k) { return sb.job[k].block_end; });
+  split_weights_elems(sb.job[at.j], (size_t)((int)blockIdx.x - at.first) * blockDim.x + threadIdx.x, (size_t)at.count * blockDim.x);
 }
 
 int launch_split_weights_multi(SplitBatch& sb, hipStream_t s) {

@@ -8,6 +8,7 @@
 
 #include "kernels.h"
 #include "conv16.h"
+#include "job_queue.h"
 
 namespace ms {
 
@@ -1759,13 +1760,11 @@ struct CopyBatch {
   size_t bytes[COPY_MULTI_MAX];
 };
 __global__ __launch_bounds__(256) void copy_multi_kernel(const CopyBatch cb) {
-  int j = 0;
-  while (j + 1 < cb.n && (int)blockIdx.x >= cb.block_end[j]) ++j;
-  const int b0 = j ? cb.block_end[j - 1] : 0;
-  const size_t off = ((size_t)((int)blockIdx.x - b0) * 256 + threadIdx.x) * 64;      // 64 bytes per thread
-  const char* s = cb.src[j];
-  char* d = cb.dst[j];
-  const size_t n = cb.bytes[j];
+  const JobSlot at = find_job(cb.n, (int)blockIdx.x, [&](int k) { return cb.block_end[k]; });
+  const size_t off = ((size_t)((int)blockIdx.x - at.first) * 256 + threadIdx.x) * 64;      // 64 bytes per thread
+  const char* s = cb.src[at.j];
+  char* d = cb.dst[at.j];
+  const size_t n = cb.bytes[at.j];
   if (off >= n) return;
   if (((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d)) & 15) == 0 && off + 64 <= n) {
     const uint4* s4 = reinterpret_cast<const uint4*>(s + off);

@@ -13,10 +13,10 @@
 // [8 blocks][TH][(TW-1)*S + TP] as 16-byte vectors.  Pixel splits leave fp32 partial slabs that are summed in a fixed order
 // by the caller (ms_wgrad_reduce_multi), like the fp32 kernels'.
 #include <algorithm>
-#include <mutex>
 #include <vector>
 
 #include "conv16_kernel.h"
+#include "job_queue.h"
 
 namespace ms {
 
@@ -342,11 +342,9 @@ template <typename DT, int TP, bool UP2, int NPXT>
 __global__ __launch_bounds__(256) void wgrad16_multi_kernel(const Wgrad16Batch b) {
   extern __shared__ u32x4 smem[];
   prefetch_kernargs<128>();                                   // n and the table of block ranges
-  int j = 0;
-  while (j + 1 < b.n && (int)blockIdx.x >= b.block_end[j]) ++j;
-  const int b0 = j ? b.block_end[j - 1] : 0;
-  prefetch_kernargs<sizeof(Wgrad16Args)>((int)offsetof(Wgrad16Batch, job) + j * (int)sizeof(Wgrad16Args));
-  wgrad16_body<DT, TP, UP2, NPXT>(b.job[j], (int)blockIdx.x - b0, smem);
+  const JobSlot at = find_job(b.n, (int)blockIdx.x, [&](int k) { return b.block_end[k]; });
+  prefetch_kernargs<sizeof(Wgrad16Args)>((int)offsetof(Wgrad16Batch, job) + at.j * (int)sizeof(Wgrad16Args));
+  wgrad16_body<DT, TP, UP2, NPXT>(b.job[at.j], (int)blockIdx.x - at.first, smem);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -695,8 +693,7 @@ static double finish_wgrad16_args(const Wgrad16Args& a, const Wgrad16Plan& pl, b
 // ---- queued launches (ms_bwd_options.defer_wgrad_launch / ms_wgrad_flush)
 struct PendingWgrad16 { int dt, tp, up2, npxt, lds, nwg; double flops, bytes; Wgrad16Args a; };
 // process-wide: autograd runs the blocks' backward on its device thread and the end-of-backward callback on the caller's
-static std::vector<PendingWgrad16> t_pending;
-static std::mutex t_pending_mu;
+static PendingQueue<PendingWgrad16> t_pending;
 
 int queue_wgrad16(int dt, const Wgrad16Args& a, const Wgrad16Plan& pl, bool up2, double flops, double bytes) {
   PendingWgrad16 pw;
@@ -706,62 +703,27 @@ int queue_wgrad16(int dt, const Wgrad16Args& a, const Wgrad16Plan& pl, bool up2,
   // accumulated the parameter's other uses of this step into the same slot (the slot starts the step zeroed)
   if (pl.splits == 1) pw.a.accumulate = 1;
   pw.dt = dt; pw.tp = up2 ? 3 : pl.tp; pw.up2 = up2 ? 1 : 0; pw.npxt = up2 ? 0 : wg16_npxt_queued(pl.npx); pw.lds = pl.lds_bytes; pw.nwg = (int)nwg; pw.flops = flops; pw.bytes = bytes;
-  std::lock_guard<std::mutex> lk(t_pending_mu);
-  t_pending.push_back(pw);
+  t_pending.push(pw);
   return 0;
 }
 
-void wgrad16_discard() {
-  std::lock_guard<std::mutex> lk(t_pending_mu);
-  t_pending.clear();
-}
+void wgrad16_discard() { t_pending.discard(); }
 
+// one launch per kernel instance (element type, taps per row, input form, slots) and per WG16_MAX_JOBS jobs, in queue order
 int wgrad16_flush(hipStream_t s) {
-  // one launch per kernel instance (element type, taps per row, input form) and per WG16_MAX_JOBS blocks, in queue order
-  std::vector<PendingWgrad16> q;
-  {
-    std::lock_guard<std::mutex> lk(t_pending_mu);
-    q.swap(t_pending);
-  }
-  std::vector<char> done(q.size(), 0);
-  for (size_t i = 0; i < q.size(); ++i) {
-    if (done[i]) continue;
-    Wgrad16Batch b;
-    b.n = 0;
-    int lds = 0;
-    long blocks = 0;
-    double flops = 0, bytes = 0;
-    auto launch = [&]() -> int {
-      if (!b.n) return 0;
-      TimingScope ts(s, flops, bytes, "wgrad16_multi_kernel<%s,%d,%d>|conv_wgrad_cb8 multi taps%d up%d jobs%d wgs%ld",
-                     q[i].dt == DT_BF16 ? "bf16" : "f16", q[i].tp, q[i].up2, q[i].tp, q[i].up2, b.n, blocks);
-      int rc = 0;
-      if (!ts.skip()) {
-        rc = q[i].dt == DT_BF16 ? launch_tp_multi<BF16>(b, q[i].tp, q[i].up2 != 0, q[i].npxt, lds, s)
-                                : launch_tp_multi<F16>(b, q[i].tp, q[i].up2 != 0, q[i].npxt, lds, s);
-        if (!rc) rc = check_launch("wgrad16_multi_kernel");
-      }
-      b.n = 0; lds = 0; blocks = 0; flops = bytes = 0;
-      return rc;
-    };
-    for (size_t k = i; k < q.size(); ++k) {
-      if (done[k] || q[k].dt != q[i].dt || q[k].tp != q[i].tp || q[k].up2 != q[i].up2 || q[k].npxt != q[i].npxt) continue;
-      if (b.n == WG16_MAX_JOBS || blocks + q[k].nwg > 0x3fffffff) {
-        const int rc = launch();
-        if (rc) return rc;
-      }
-      blocks += q[k].nwg;
-      b.block_end[b.n] = (int)blocks;
-      b.job[b.n] = q[k].a;
-      ++b.n;
-      lds = std::max(lds, q[k].lds);
-      flops += q[k].flops; bytes += q[k].bytes;
-      done[k] = 1;
-    }
-    const int rc = launch();
-    if (rc) return rc;
-  }
-  return 0;
+  return pack_jobs<Wgrad16Batch>(
+      t_pending.take(),
+      [](const PendingWgrad16& x, const PendingWgrad16& h) { return x.dt == h.dt && x.tp == h.tp && x.up2 == h.up2 && x.npxt == h.npxt; },
+      [s](const PendingWgrad16& h, const Wgrad16Batch& b, const std::vector<const PendingWgrad16*>& jobs, const JobTotals& t) -> int {
+        TimingScope ts(s, t.flops, t.bytes, "wgrad16_multi_kernel<%s,%d,%d>|conv_wgrad_cb8 multi taps%d up%d jobs%d wgs%ld",
+                       h.dt == DT_BF16 ? "bf16" : "f16", h.tp, h.up2, h.tp, h.up2, b.n, t.wgs);
+        if (ts.skip()) return 0;
+        int lds = 0;
+        for (const PendingWgrad16* w : jobs) lds = std::max(lds, w->lds);
+        const int rc = h.dt == DT_BF16 ? launch_tp_multi<BF16>(b, h.tp, h.up2 != 0, h.npxt, lds, s)
+                                       : launch_tp_multi<F16>(b, h.tp, h.up2 != 0, h.npxt, lds, s);
+        return rc ? rc : check_launch("wgrad16_multi_kernel");
+      });
 }
 
 int launch_wgrad16(int dt, const Wgrad16Args& a, const Wgrad16Plan& pl, bool up2, double flops, double bytes, hipStream_t s) {

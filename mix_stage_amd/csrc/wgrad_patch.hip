@@ -7,10 +7,10 @@
 // pixel offset, so the inner loop is ds_read_b32 with immediate offsets + v_mfma_f32_32x32x2_f32.  Patch pitches are
 // chosen so that consecutive columns n fall in consecutive LDS banks (row pitch = KW, channel pitch = KH*KW mod 32).
 #include <algorithm>
-#include <mutex>
 #include <vector>
 
 #include "kernels.h"
+#include "job_queue.h"
 
 namespace ms {
 
@@ -205,11 +205,9 @@ __global__ __launch_bounds__(256) void wgrad_patch_kernel(const WgradPatchArgs p
 template <int KH, int KW, int S, int TW, bool UP2>
 __global__ __launch_bounds__(256) void wgrad_patch_multi_kernel(const WgradPatchBatch b) {
   prefetch_kernargs<128>();                                   // n and the table of block ranges
-  int j = 0;
-  while (j + 1 < b.n && (int)blockIdx.x >= b.block_end[j]) ++j;
-  const int b0 = j ? b.block_end[j - 1] : 0;
-  prefetch_kernargs<sizeof(WgradPatchArgs)>((int)offsetof(WgradPatchBatch, job) + j * (int)sizeof(WgradPatchArgs));
-  wgrad_patch_body<KH, KW, S, TW, UP2>(b.job[j], (int)blockIdx.x - b0);
+  const JobSlot at = find_job(b.n, (int)blockIdx.x, [&](int k) { return b.block_end[k]; });
+  prefetch_kernargs<sizeof(WgradPatchArgs)>((int)offsetof(WgradPatchBatch, job) + at.j * (int)sizeof(WgradPatchArgs));
+  wgrad_patch_body<KH, KW, S, TW, UP2>(b.job[at.j], (int)blockIdx.x - at.first);
 }
 
 // =============================================================================================
@@ -511,12 +509,10 @@ __device__ __forceinline__ void wgrad_wave_body(const WgradPatchArgs& p, const i
 __global__ __launch_bounds__(256, 3) void wgrad_wave_multi_kernel(const WgradPatchBatch b) {
   extern __shared__ float wave_smem[];
   prefetch_kernargs<128>();
-  int j = 0;
-  while (j + 1 < b.n && (int)blockIdx.x >= b.block_end[j]) ++j;
-  const int b0 = j ? b.block_end[j - 1] : 0;
-  prefetch_kernargs<sizeof(WgradPatchArgs)>((int)offsetof(WgradPatchBatch, job) + j * (int)sizeof(WgradPatchArgs));
-  const WgradPatchArgs& p = b.job[j];
-  const int bid = (int)blockIdx.x - b0;
+  const JobSlot at = find_job(b.n, (int)blockIdx.x, [&](int k) { return b.block_end[k]; });
+  prefetch_kernargs<sizeof(WgradPatchArgs)>((int)offsetof(WgradPatchBatch, job) + at.j * (int)sizeof(WgradPatchArgs));
+  const WgradPatchArgs& p = b.job[at.j];
+  const int bid = (int)blockIdx.x - at.first;
   switch (p.wave_kind) {            // stride * 2 + (tile == 64 x 256); 6, 7: stride 1, 128 x 128, MODE 1 / 2
     case 2: wgrad_wave_body<1, 2, 2>(p, bid, wave_smem); break;
     case 3: wgrad_wave_body<1, 1, 4>(p, bid, wave_smem); break;
@@ -682,8 +678,7 @@ static void launch_wgpm_tw(const WgradPatchBatch& b, int tw, hipStream_t s) {
 }
 
 struct PendingWgradPatch { int KH, KW, S, tw, up2, nwg, wave; double flops, bytes; WgradPatchArgs a; };
-static std::vector<PendingWgradPatch> g_pending;     // process-wide (autograd's device thread queues, the caller's thread flushes)
-static std::mutex g_pending_mu;
+static PendingQueue<PendingWgradPatch> g_pending;
 
 int queue_wgrad_patch(const WgradPatchArgs& a, const WgradPatchPlan& pl, int KH, int KW, int S, bool up2, double flops, double bytes) {
   PendingWgradPatch pw;
@@ -703,49 +698,30 @@ int queue_wgrad_patch(const WgradPatchArgs& a, const WgradPatchPlan& pl, int KH,
     pw.KH = pw.KW = pw.S = 0; pw.up2 = 0;      // every shape shares the one launch
     pw.tw = 0;                       // one instance per kernel shape: the 16-pixel steps do not depend on the tile width
   }
-  std::lock_guard<std::mutex> lk(g_pending_mu);
-  g_pending.push_back(pw);
+  g_pending.push(pw);
   return 0;
 }
 
-void wgrad_patch_discard() {
-  std::lock_guard<std::mutex> lk(g_pending_mu);
-  g_pending.clear();
-}
+void wgrad_patch_discard() { g_pending.discard(); }
 
+// one launch per kernel instance (shape, tile width, input form; every lean-kernel job shares one) and per WGP_MAX_JOBS jobs
 int wgrad_patch_flush(hipStream_t s) {
-  std::vector<PendingWgradPatch> q;
-  {
-    std::lock_guard<std::mutex> lk(g_pending_mu);
-    q.swap(g_pending);
-  }
+  std::vector<PendingWgradPatch> q = g_pending.take();
   // workgroups are dispatched in id order: the layers whose workgroups run longest go first, so the launch's tail is made of
-  // short ones (stable: equal lengths keep their queue order)
-  std::stable_sort(q.begin(), q.end(), [](const PendingWgradPatch& x, const PendingWgradPatch& y) {
-    const int lx = x.wave ? 4 * x.a.steps_per_split : 4 * x.a.tiles_per_split, ly = y.wave ? 4 * y.a.steps_per_split : 4 * y.a.tiles_per_split;
-    return lx > ly;
-  });
-  std::vector<char> done(q.size(), 0);
-  for (size_t i = 0; i < q.size(); ++i) {
-    if (done[i]) continue;
-    WgradPatchBatch b;
-    b.n = 0;
-    long blocks = 0;
-    double flops = 0, bytes = 0;
-    const PendingWgradPatch& h = q[i];
-    auto launch = [&]() -> int {
-      if (!b.n) return 0;
-      TimingScope ts(s, flops, bytes, "%s<%d,%d,%d,%d,%d>|conv_wgrad_%s multi k%dx%d s%d tw%d up%d jobs%d wgs%ld",
-                     h.wave ? "wgrad_wave_multi_kernel" : "wgrad_patch_multi_kernel", h.KH, h.KW, h.S, h.tw, h.up2,
-                     h.wave ? "wave" : "patch", h.KH, h.KW, h.S, h.tw, h.up2, b.n, blocks);
-      int rc = 0;
-      if (!ts.skip()) {
+  // short ones (equal lengths keep their queue order)
+  sort_jobs(q, [](const PendingWgradPatch& x) { return -(x.wave ? 4 * x.a.steps_per_split : 4 * x.a.tiles_per_split); });
+  return pack_jobs<WgradPatchBatch>(
+      q,
+      [](const PendingWgradPatch& x, const PendingWgradPatch& h) {
+        return x.KH == h.KH && x.KW == h.KW && x.S == h.S && x.tw == h.tw && x.up2 == h.up2 && (x.wave != 0) == (h.wave != 0);
+      },
+      [s](const PendingWgradPatch& h, const WgradPatchBatch& b, const std::vector<const PendingWgradPatch*>&, const JobTotals& t) -> int {
+        TimingScope ts(s, t.flops, t.bytes, "%s<%d,%d,%d,%d,%d>|conv_wgrad_%s multi k%dx%d s%d tw%d up%d jobs%d wgs%ld",
+                       h.wave ? "wgrad_wave_multi_kernel" : "wgrad_patch_multi_kernel", h.KH, h.KW, h.S, h.tw, h.up2,
+                       h.wave ? "wave" : "patch", h.KH, h.KW, h.S, h.tw, h.up2, b.n, t.wgs);
+        if (ts.skip()) return 0;
+        if (h.wave) return launch_wave(b, s);
         const int KH = h.KH, KW = h.KW, S = h.S;
-        if (h.wave) {
-          rc = launch_wave(b, s);
-          b.n = 0; blocks = 0; flops = bytes = 0;
-          return rc;
-        }
         if (KH == 1 && KW == 3 && S == 1) {
           if (h.up2) launch_wgpm_tw<1, 3, 1, true>(b, h.tw, s);
           else launch_wgpm_tw<1, 3, 1, false>(b, h.tw, s);
@@ -755,28 +731,8 @@ int wgrad_patch_flush(hipStream_t s) {
         else if (KH == 3 && KW == 3 && S == 1) launch_wgpm_tw<3, 3, 1, false>(b, h.tw, s);
         else if (KH == 4 && KW == 4 && S == 2) launch_wgpm_tw<4, 4, 2, false>(b, h.tw, s);
         else launch_wgpm_tw<3, 8, 1, false>(b, h.tw, s);
-        rc = check_launch("wgrad_patch_multi_kernel");
-      }
-      b.n = 0; blocks = 0; flops = bytes = 0;
-      return rc;
-    };
-    for (size_t k = i; k < q.size(); ++k) {
-      if (done[k] || q[k].KH != h.KH || q[k].KW != h.KW || q[k].S != h.S || q[k].tw != h.tw || q[k].up2 != h.up2 || (q[k].wave != 0) != (h.wave != 0)) continue;
-      if (b.n == WGP_MAX_JOBS || blocks + q[k].nwg > 0x3fffffff) {
-        const int rc = launch();
-        if (rc) return rc;
-      }
-      blocks += q[k].nwg;
-      b.block_end[b.n] = (int)blocks;
-      b.job[b.n] = q[k].a;
-      ++b.n;
-      flops += q[k].flops; bytes += q[k].bytes;
-      done[k] = 1;
-    }
-    const int rc = launch();
-    if (rc) return rc;
-  }
-  return 0;
+        return check_launch("wgrad_patch_multi_kernel");
+      });
 }
 
 int launch_wgrad_patch(const WgradPatchArgs& a, const WgradPatchPlan& pl, int KH, int KW, int S, bool up2, double flops,

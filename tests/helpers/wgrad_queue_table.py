@@ -23,7 +23,7 @@ The mirrors restate the host code that decides where a block's weight gradient r
   plan_wgrad_patch + wgrad_wave_ok + wave_setup   csrc/wgrad_patch.hip   (family wave / patch, else gather; wave_kind; splits)
   wgrad_splits, shape_of                          csrc/conv_igemm.hip    (gather kernel: splits, kernel shape 0..4)
   plan_wgrad16, wg16_npxt_queued                  csrc/wgrad16.hip       (16-bit: taps, slots, splits)
-  the three flush routines                        (jobs per launch, rollover at the job limit)
+  pack_jobs + the three flush routines            csrc/job_queue.h       (jobs per launch, rollover at the job limit)
   launch_reduce_splits_multi                      csrc/conv_igemm.hip    (wave / 16-byte / scalar form, blocks per job)"""
 import re
 
@@ -33,6 +33,7 @@ from helpers.dispatch_table import TABLE as DISPATCH
 WGP_MAX_JOBS = 48              # csrc/kernels.h
 WG_MAX_JOBS = 24               # csrc/kernels.h
 WG16_MAX_JOBS = 20             # csrc/conv16.h
+MAX_LAUNCH_WGS = 0x3fffffff    # csrc/job_queue.h
 REDUCE_BATCH_MAX = 96          # csrc/kernels.h
 WGRAD_STEPS_PER_WG = 96        # csrc/wgrad_patch.hip g_wgrad_steps_per_wg
 WGRAD_MIN_WGS = 48             # csrc/wgrad_patch.hip g_wgrad_min_wgs
@@ -272,14 +273,27 @@ def _label_regex(queue, jobs, wgs):
 
 def flush_launches(plans):
   """The multi-job launches one ms_wgrad_flush makes of these queued jobs (given in queue order) -> [(queue key, [job indices])].
-  wgrad_patch_flush stable-sorts by workgroup length (longest first) and takes the jobs of the first unlaunched job's instance,
-  WGP_MAX_JOBS at a time; wgrad_gather_flush walks the five shapes, WG_MAX_JOBS at a time; wgrad16_flush groups by
-  (type, taps, input form, slots) in queue order, WG16_MAX_JOBS at a time."""
+  The packing rule is pack_jobs in csrc/job_queue.h (tests/test_job_queue_cpu.py runs it against this mirror without a GPU): the jobs
+  of the first unlaunched job's instance, in order, a launch ending at the family's job limit or before the job that would take its
+  workgroups past MAX_LAUNCH_WGS.  wgrad_patch_flush first stable-sorts by workgroup length (longest first), WGP_MAX_JOBS at a time;
+  wgrad_gather_flush goes by shape 0..4, WG_MAX_JOBS at a time; wgrad16_flush groups by (type, taps, input form, slots) in queue
+  order, WG16_MAX_JOBS at a time."""
   out = []
   patch = [i for i, p in enumerate(plans) if p['queued'] and p['family'] in ('wave', 'patch')]
   patch.sort(key=lambda i: -plans[i]['length'])                    # (sorted() is stable, like std::stable_sort)
   gather = [i for i, p in enumerate(plans) if p['queued'] and p['family'] == 'gather']
   h16 = [i for i, p in enumerate(plans) if p['queued'] and p['family'] == 'h16']
+
+  def launches(queue, mine, limit):
+    cur, wgs = [], 0
+    for k in mine:
+      if cur and (len(cur) == limit or wgs + plans[k]['wgs'] > MAX_LAUNCH_WGS):
+        out.append((queue, cur))
+        cur, wgs = [], 0
+      cur.append(k)
+      wgs += plans[k]['wgs']
+    if cur:
+      out.append((queue, cur))
 
   def by_head(order, limit):
     done = set()
@@ -288,13 +302,10 @@ def flush_launches(plans):
         continue
       mine = [k for k in order if k not in done and plans[k]['queue'] == plans[i]['queue']]
       done.update(mine)
-      for at in range(0, len(mine), limit):
-        out.append((plans[i]['queue'], mine[at:at + limit]))
+      launches(plans[i]['queue'], mine, limit)
   by_head(patch, WGP_MAX_JOBS)
   for shape in range(5):
-    mine = [i for i in gather if plans[i]['queue'][1] == shape]
-    for at in range(0, len(mine), WG_MAX_JOBS):
-      out.append((('gather', shape), mine[at:at + WG_MAX_JOBS]))
+    launches(('gather', shape), [i for i in gather if plans[i]['queue'][1] == shape], WG_MAX_JOBS)
   by_head(h16, WG16_MAX_JOBS)
   return out
 
