@@ -67,6 +67,11 @@ enum ms_dtype { MS_F32 = 0, MS_BF16 = 1, MS_F16 = 2 };
  * weights are the sum over both halves, which is what two separate backward passes accumulate.  B must be even.
  * ms_stat_pair_ok(d) says whether block d's kernels implement the flag. */
 #define MS_DT_STAT_PAIR 0x400
+/* MS_DT_BN_FROZEN (flag, BN_EVAL blocks, every arithmetic mode): the DIFFERENTIABLE form of a block that normalises with its running statistics
+ * (frozen BatchNorm, what nn.BatchNorm*.eval() is under autograd): the forward keeps y_raw and writes `save` from the running
+ * statistics, ms_conv_block_bwd differentiates it (see both).  Without the flag a BN_EVAL forward is the one-launch eval form and
+ * ignores y_raw / save, as it always did. */
+#define MS_DT_BN_FROZEN 0x800
 
 /* Geometry of one conv block (1-D convs use H = KH = SH = 1, PH = 0). */
 typedef struct ms_conv_desc {
@@ -115,9 +120,16 @@ size_t ms_conv_block_bwd_workspace(const ms_conv_desc* d);
  *   x2       UP2ADD only: residual r (B, groups*Cin, W); else NULL
  *   w        (groups*Cout, Cin, KH, KW)   bias (groups*Cout)
  *   gamma,beta,running_mean,running_var   (groups*Cout)   BN modes only; running_* updated in BN_TRAIN
- *   y_raw    BN_TRAIN only: conv+bias output kept for backward, same shape as y
+ *   y_raw    BN_TRAIN, and BN_EVAL with MS_DT_BN_FROZEN: conv+bias output kept for backward, same shape as y; else ignored
  *   y        (B, groups*Cout, OH, OW) block output
- *   save     BN_TRAIN only: 4*groups*Cout floats = mean | invstd | scale | shift
+ *   save     BN_TRAIN, and BN_EVAL with MS_DT_BN_FROZEN: 4*groups*Cout floats = mean | invstd | scale | shift
+ * BN_EVAL with MS_DT_BN_FROZEN (frozen BatchNorm, the differentiable form): the conv runs as the block's MS_BARE launch
+ * into y_raw; one launch then writes `save` from the running statistics -- invstd = 1/sqrt(running_var + eps), scale = gamma *
+ * invstd, shift = beta - running_mean * scale, in fp32 -- normalises and activates.  running_mean / running_var are only read.
+ * y_raw, `save` and the workspace are required; MS_DT_BN_FOLDED with it is an error (nothing is left to differentiate);
+ * MS_DT_STAT_PAIR means a plain batch of B, the block has no statistics groups (ms_stat_pair_ok keeps answering for BN_TRAIN);
+ * ms_conv_block_fwd_workspace names the bytes of this form too.  Every arithmetic mode: in the
+ * 16-bit modes y_raw is cb8, y cb8 or plain fp32 with MS_DT_OUT_F32 (the apply launch honours it), `save` fp32 as ever.
  * Alignment: every tensor starts on a 16-byte boundary (what any allocator of device memory returns; torch's are 256-byte aligned).
  * The kernels load 16 bytes per lane wherever a row allows it; the 2-D layers with at least 256 output tiles have no other form, and a
  * call that hands them an odd pointer (a sliced view with an element offset) returns an error that names it instead of computing.
@@ -177,7 +189,14 @@ int ms_fwd_weights_prepare(int n, const ms_conv_desc* descs, const float* const*
 
 /* Backward of the same block (what autograd derives for layers.py:78 in the reference).
  *   dy       grad wrt y.
- *   y_raw/save as produced by the forward (BN_TRAIN); y (LRELU mode mask); BN_EVAL uses running stats.
+ *   y_raw/save as produced by the forward (BN_TRAIN, and BN_EVAL in its differentiable form); y (LRELU mode mask).
+ * BN_EVAL (the forward ran with MS_DT_BN_FROZEN, the flag itself is optional here): the backward of the frozen-statistics
+ * block.  Needs y_raw, save, gamma and dyr.  With z = y_raw*scale + shift:
+ *   dz = dy * (z > 0 ? 1 : slope), dy_raw = dz * gamma * invstd, dgamma = sum(dz * x_hat), dbeta = sum(dz), dbias = sum(dy_raw)
+ * -- the BN_TRAIN kernels without the two batch-mean terms; the data and weight gradients behind it run as in every mode
+ * (wt_prepared, wgrad_partials, defer_wgrad_launch, dx_accum, prev_* naming a BN_TRAIN producer).  Refused: dy_is_dyr (a frozen
+ * block is never a fused producer: prev_* of another call must not name one -- the fused launch applies the batch-statistics
+ * form and cannot tell) and the side-stream form.  running_mean / running_var are not read here.
  *   dyr      scratch, same shape as y: grad wrt the raw conv output (returned for inspection)
  *   dx       grad wrt x  (UP2ADD: grad wrt a, (B, groups*Cin, W/2)); NULL = skip
  *   dx2      UP2ADD: grad wrt r; else NULL

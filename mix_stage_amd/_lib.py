@@ -66,6 +66,7 @@ class Prep16Item(ctypes.Structure):
 
 
 MS_BARE, MS_LRELU, MS_BN_TRAIN, MS_BN_EVAL = 0, 1, 2, 3
+MS_DT_BN_FROZEN = 0x800      # BN_EVAL blocks: the differentiable (frozen-statistics) form, include/mixstage.h
 MS_IN_PLAIN, MS_IN_BCAST, MS_IN_UP2ADD = 0, 1, 2
 MS_F32, MS_BF16, MS_F16, MS_DT_OUT_F32, MS_DT_BN_FOLDED = 0, 1, 2, 0x100, 0x200
 MS_DT_STAT_PAIR = 0x400      # BN_TRAIN statistics per half of the batch (two passes of a module side by side: include/mixstage.h)

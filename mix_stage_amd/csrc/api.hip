@@ -18,8 +18,9 @@ static int validate(const ms_conv_desc* d, const char* who) {
   if (d->in_mode < MS_IN_PLAIN || d->in_mode > MS_IN_UP2ADD) return set_error("%s: bad in_mode %d", who, d->in_mode);
   if (d->in_mode == MS_IN_UP2ADD && (d->H != 1 || d->KH != 1 || (d->W & 1)))
     return set_error("%s: UP2ADD needs a 1-D block with even W", who);
-  if (dt_of(d) > DT_F16 || (d->dtype & ~(0xff | MS_DT_OUT_F32 | MS_DT_BN_FOLDED | MS_DT_STAT_PAIR))) return set_error("%s: bad dtype 0x%x", who, d->dtype);
-  if (dt_of(d) == DT_F32 && (d->dtype & ~(0xff | MS_DT_STAT_PAIR))) return set_error("%s: MS_DT_OUT_F32 is a flag of the 16-bit modes", who);
+  if (dt_of(d) > DT_F16 || (d->dtype & ~(0xff | MS_DT_OUT_F32 | MS_DT_BN_FOLDED | MS_DT_STAT_PAIR | MS_DT_BN_FROZEN))) return set_error("%s: bad dtype 0x%x", who, d->dtype);
+  if (dt_of(d) == DT_F32 && (d->dtype & ~(0xff | MS_DT_STAT_PAIR | MS_DT_BN_FROZEN))) return set_error("%s: MS_DT_OUT_F32 is a flag of the 16-bit modes", who);
+  if ((d->dtype & MS_DT_BN_FROZEN) && d->mode != MS_BN_EVAL) return set_error("%s: MS_DT_BN_FROZEN is a flag of BN_EVAL blocks", who);
   if ((d->dtype & MS_DT_STAT_PAIR) && (d->B & 1)) return set_error("%s: MS_DT_STAT_PAIR needs an even batch", who);
   const double out_elems = (double)d->B * d->groups * d->Cout * d->OH * d->OW;
   const double in_elems = (double)d->B * d->groups * d->Cin * d->H * d->W;
@@ -208,6 +209,24 @@ static int conv_block_fwd_impl(const ms_conv_desc* d, const float* x, const floa
   if (bn && (!gamma || !beta || !running_mean || !running_var)) return set_error("ms_conv_block_fwd: BN tensors missing");
   if (d->mode == MS_BN_TRAIN && (!y_raw || !save || !workspace)) return set_error("ms_conv_block_fwd: y_raw/save/workspace missing");
   if (d->in_mode == MS_IN_UP2ADD && !x2) return set_error("ms_conv_block_fwd: UP2ADD needs x2");
+  // BN_EVAL with MS_DT_BN_FROZEN: the differentiable (frozen-statistics) form -- the conv as its MS_BARE launch into y_raw, then ONE
+  // launch that writes `save` from the running statistics, normalises and activates.  The running statistics are only read.
+  // (Without the flag a BN_EVAL block is the one-launch eval form whatever y_raw / save point to, as it always was.)
+  const bool frozen = d->mode == MS_BN_EVAL && (d->dtype & MS_DT_BN_FROZEN);
+  if (frozen && (d->dtype & MS_DT_BN_FOLDED)) return set_error("ms_conv_block_fwd: MS_DT_BN_FOLDED with MS_DT_BN_FROZEN: a folded block has no BatchNorm to differentiate");
+  if (frozen && (!y_raw || !save || !workspace)) return set_error("ms_conv_block_fwd: MS_DT_BN_FROZEN (the differentiable BN_EVAL form) needs y_raw/save/workspace");
+  if (frozen && dt_of(d) == DT_F32) {
+    ms_conv_desc bare = *d;
+    bare.mode = MS_BARE;
+    bare.dtype &= ~(MS_DT_STAT_PAIR | MS_DT_BN_FROZEN);          // (no statistics groups: a plain batch of B)
+    if (workspace_bytes < fwd_plan(d).ws.total) return set_error("ms_conv_block_fwd: workspace too small");
+    rc = conv_block_fwd_impl(&bare, x, x2, w, bias, nullptr, nullptr, nullptr, nullptr, nullptr, y_raw, nullptr, workspace, workspace_bytes, stream, opt);
+    if (!rc) rc = clip32_hold_flush((hipStream_t)stream);      // (the conv's launch is on the stream before its reader)
+    if (rc) return rc;
+    const BlockGeo g = geo_of(d);
+    return launch_bn_apply_frozen(y_raw, y, save, gamma, beta, running_mean, running_var, d->eps, g.C, g.hw, (size_t)g.npix * g.C, d->slope,
+                                  (hipStream_t)stream);
+  }
   if (dt_of(d) != DT_F32)     // 16-bit modes: the tensor pointers are cb8 buffers (include/mixstage.h, ms_dtype)
     return block_fwd16(d, x, x2, w, bias, gamma, beta, running_mean, running_var, y_raw, y, save, workspace, workspace_bytes,
                        (hipStream_t)stream, w_planes, opt ? opt->bn_sync : nullptr, opt ? opt->bn_sync_words : 0);
@@ -544,8 +563,12 @@ static int conv_block_bwd_impl(const ms_conv_desc* d, const float* x, const floa
   const float* wt_prepared = opt->wt_prepared;
   const bool defer_wgrad = opt->wgrad_partials != nullptr;
   int rc = 0;                                      // (d is validated: ms_conv_block_bwd_ex)
-  if (d->mode == MS_BN_EVAL) return set_error("ms_conv_block_bwd: BN_EVAL blocks are never differentiated on the path");
   if (!dy || !w || !workspace) return set_error("ms_conv_block_bwd: null tensor");
+  // BN_EVAL: the frozen-statistics block (forward: BN_EVAL with y_raw).  Only step 1 below knows the mode.
+  const bool frozen = d->mode == MS_BN_EVAL;
+  if (frozen && (!y_raw || !save || !gamma || !dyr)) return set_error("ms_conv_block_bwd: BN_EVAL (frozen statistics) needs y_raw/save/gamma/dyr");
+  if (frozen && opt->dy_is_dyr) return set_error("ms_conv_block_bwd: dy_is_dyr on a BN_EVAL block: a frozen block is never a fused producer");
+  if (frozen && side_stream && side_stream != stream) return set_error("ms_conv_block_bwd: no side-stream form for BN_EVAL (frozen statistics) blocks");
   if (d->mode == MS_BN_TRAIN && !opt->dy_is_dyr && (!y_raw || !save || !gamma || !dyr)) return set_error("ms_conv_block_bwd: BN_TRAIN needs y_raw/save/gamma/dyr");
   if ((opt->dy_is_dyr || opt->prev_y) && (dt_of(d) != DT_F32 || side_stream)) return set_error("ms_conv_block_bwd: the fused producer-BatchNorm backward is an fp32, single-stream form");
   if (d->mode == MS_LRELU && (!y || !dyr)) return set_error("ms_conv_block_bwd: LRELU needs y/dyr");
@@ -596,6 +619,9 @@ static int conv_block_bwd_impl(const ms_conv_desc* d, const float* x, const floa
     bias_done = 1;
   } else if (d->mode == MS_BN_TRAIN) {
     rc = launch_bn_bwd(dy, y_raw, y, save, gamma, bn_part, dyr, colpart, dbias, dgamma, dbeta, d->B, C, hw, d->slope, &bias_done, s, sg_of(d));
+    gr = dyr;
+  } else if (frozen) {
+    rc = launch_bn_bwd(dy, y_raw, nullptr, save, gamma, bn_part, dyr, colpart, dbias, dgamma, dbeta, d->B, C, hw, d->slope, &bias_done, s, 1, true);
     gr = dyr;
   } else if (d->mode == MS_LRELU) {
     rc = launch_act_bwd(dy, y, dyr, colpart, dbias, d->B, C, hw, 1, d->slope, &bias_done, s);

@@ -133,6 +133,21 @@ int block_fwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
                 size_t workspace_bytes, hipStream_t s, const void* w_prepared, int32_t* bn_sync, int bn_sync_words) {
   const BlockGeo g = geo_of(d);
   if (g.dt != DT_BF16 && g.dt != DT_F16) return set_error("ms_conv_block_fwd: dtype %d", d->dtype);
+  if (d->mode == MS_BN_EVAL && (d->dtype & MS_DT_BN_FROZEN)) {
+    // frozen BatchNorm, the differentiable form (api.hip checked y_raw / save / workspace): the conv as its MS_BARE launch into the
+    // cb8 y_raw, then ONE launch that writes `save` from the running statistics, normalises and activates (cb8, or fp32 with
+    // MS_DT_OUT_F32).  No statistics groups: MS_DT_STAT_PAIR is a plain batch of B.
+    if (workspace_bytes < block_fwd16_workspace(d)) return set_error("ms_conv_block_fwd: workspace too small");
+    ms_conv_desc bare = *d;
+    bare.mode = MS_BARE;
+    bare.dtype &= ~(MS_DT_STAT_PAIR | MS_DT_BN_FROZEN | MS_DT_OUT_F32);
+    const int rc = block_fwd16(&bare, x, x2, w, bias, nullptr, nullptr, nullptr, nullptr, nullptr, y_raw, nullptr, workspace, workspace_bytes, s,
+                               w_prepared, bn_sync, bn_sync_words);
+    if (rc) return rc;
+    const bool f32 = out_f32_of(d);
+    return launch_bn_apply16_frozen(g.dt, y_raw, f32 ? nullptr : y, f32 ? (float*)y : nullptr, save, gamma, beta, running_mean, running_var,
+                                    d->eps, d->B, g.C, g.hw, d->slope, s);
+  }
   if (d->mode == MS_BN_TRAIN && sg_of(d) > 1 && !stat_pair16_ok(d))
     return set_error("ms_conv_block_fwd: MS_DT_STAT_PAIR is not implemented for this 16-bit block (ms_stat_pair_ok)");
   if (!bn_sync) { bn_sync = g_bn_sync; bn_sync_words = g_bn_sync_n; }      // (the process-wide buffer of ms_set_bn_sync_buffer)
@@ -258,6 +273,11 @@ int block_bwd16(const ms_conv_desc* d, const void* x, const void* x2, const floa
     // (y: blocks with a cb8 output read x_hat and the activation mask from it wherever the map inverts safely -- conv16.h)
     rc = launch_bn_bwd16(g.dt, outf32 ? nullptr : dy, dyf, y_raw, outf32 ? nullptr : y, save, gamma, bn_part, dyr, colpart, dbias, dgamma, dbeta, d->B, g.C,
                          g.hw, d->slope, &bias_done, s, sg_of(d));
+    gsrc = dyr;
+  } else if (d->mode == MS_BN_EVAL) {
+    // frozen BatchNorm: `save` holds the running statistics (block_fwd16), y_raw is whole
+    rc = launch_bn_bwd16(g.dt, outf32 ? nullptr : dy, dyf, y_raw, nullptr, save, gamma, bn_part, dyr, colpart, dbias, dgamma, dbeta, d->B, g.C,
+                         g.hw, d->slope, &bias_done, s, 1, true);
     gsrc = dyr;
   } else if (d->mode == MS_LRELU) {
     rc = launch_act_bwd16(g.dt, dy, nullptr, y, dyr, colpart, d->B, g.C, g.hw, 1, d->slope, s);

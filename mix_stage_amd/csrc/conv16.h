@@ -147,6 +147,9 @@ int launch_conv16_c1(int dt, const void* x, const float* w, const float* wscale,
                      float eps, hipStream_t s);
 int launch_bn_apply16(int dt, const void* y_raw, void* y, float* y_f32, const float* save, int B, int C, int HW, float slope,
                       hipStream_t s);
+// frozen BatchNorm (the differentiable BN_EVAL block): `save` WRITTEN from the running statistics by the normalising launch itself
+int launch_bn_apply16_frozen(int dt, const void* y_raw, void* y, float* y_f32, float* save, const float* gamma, const float* beta,
+                             const float* rm, const float* rv, float eps, int B, int C, int HW, float slope, hipStream_t s);
 int bwd16_chunks(int B, int C8, int HW, int* b_per_chunk);
 int launch_bn_finalize_apply16(int dt, const float* stats, const float* counts, int n_tiles, int N, const float* gamma,
                                const float* beta, float* rm, float* rv, float* save, float eps, float momentum, const void* y_raw,
@@ -157,7 +160,7 @@ int launch_bn_finalize_apply16(int dt, const float* stats, const float* counts, 
 // and their two-pass backward reads it.
 int launch_bn_bwd16(int dt, const void* dy, const float* dy_f32, const void* y_raw, const void* y, const float* save, const float* gamma,
                     float* partial, void* dyr, float* colpart, float* dbias, float* dgamma, float* dbeta, int B, int C, int HW,
-                    float slope, int* bias_done, hipStream_t s, int sg = 1);
+                    float slope, int* bias_done, hipStream_t s, int sg = 1, bool frozen = false);
 // mode 1: dyr = dy * lrelu'(y); mode 0: dyr = dy (written only when dy arrives as fp32); colsum partials always
 int launch_act_bwd16(int dt, const void* dy, const float* dy_f32, const void* y, void* dyr, float* colpart, int B, int C, int HW,
                      int mode, float slope, hipStream_t s);

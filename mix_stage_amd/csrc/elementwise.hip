@@ -157,17 +157,33 @@ __global__ __launch_bounds__(256) void bn_finalize_apply_kernel(const float* __r
 }
 
 // y = lrelu(y_raw * scale[c] + shift[c]);  layout (B, C, HW)
+// FZ (a differentiable block that normalises with its running statistics): scale / shift come from frozen_bn() -- every thread
+// derives its channel's pair itself, no launch in front -- and the first C threads of the grid write `save` for the backward pass.
+template <bool FZ>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ y_raw, float* __restrict__ y,
-                                                       const float* __restrict__ save, int C, int HW, size_t total,
-                                                       float slope) {
+                                                       float* __restrict__ save, int C, int HW, size_t total,
+                                                       float slope, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, const float* __restrict__ rm,
+                                                       const float* __restrict__ rv, float eps) {
   prefetch_kernargs<128>();
   const float* scale = save + 2 * (size_t)C;
   const float* shift = save + 3 * (size_t)C;
+  if (FZ) {
+    for (size_t c = (size_t)blockIdx.x * 256 + threadIdx.x; c < (size_t)C; c += (size_t)gridDim.x * 256) {
+      const FrozenBN f = frozen_bn(gamma, beta, rm, rv, eps, (int)c);
+      save[c] = f.mean;
+      save[C + c] = f.invstd;
+      save[2 * (size_t)C + c] = f.sc;
+      save[3 * (size_t)C + c] = f.sh;
+    }
+  }
   if ((HW & 3) == 0) {
     const size_t total4 = total >> 2;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
       const int c = (int)(((i << 2) / HW) % C);
-      const float sc = scale[c], sh = shift[c];
+      float sc, sh;
+      if (FZ) { const FrozenBN f = frozen_bn(gamma, beta, rm, rv, eps, c); sc = f.sc; sh = f.sh; }
+      else { sc = scale[c]; sh = shift[c]; }
       float4 v = reinterpret_cast<const float4*>(y_raw)[i];
       v.x = lrelu(fmaf(v.x, sc, sh), slope);
       v.y = lrelu(fmaf(v.y, sc, sh), slope);
@@ -178,7 +194,10 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
   } else {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
       const int c = (int)((i / HW) % C);
-      y[i] = lrelu(fmaf(y_raw[i], scale[c], shift[c]), slope);
+      float sc, sh;
+      if (FZ) { const FrozenBN f = frozen_bn(gamma, beta, rm, rv, eps, c); sc = f.sc; sh = f.sh; }
+      else { sc = scale[c]; sh = shift[c]; }
+      y[i] = lrelu(fmaf(y_raw[i], sc, sh), slope);
     }
   }
 }
@@ -304,6 +323,9 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
 }
 
 //   dyr = gamma*invstd*(dz - s1/N - xh*s2/N);  colsum partial of dyr;  dgamma = s2, dbeta = s1
+// FZ (frozen BatchNorm: `save` holds the running statistics, which do not depend on the batch): dyr = gamma*invstd*dz -- the two
+// mean terms are the derivative of the batch statistics; same loads, same partial sums, same dgamma / dbeta
+template <bool FZ>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ y_raw,
                                                            const float* __restrict__ save, const float* __restrict__ gamma,
                                                            const float* __restrict__ partial, float* __restrict__ dyr,
@@ -330,7 +352,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     const float z = fmaf(yr, sc, sh);
     const float dz = dy[off] * (z > 0.f ? 1.f : slope);
     const float xh = (yr - mean) * invstd;
-    const float v = gi * (dz - m1 - xh * m2);
+    const float v = FZ ? gi * dz : gi * (dz - m1 - xh * m2);
     dyr[off] = v;
     cs += v;
   }
@@ -393,6 +415,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce4_kernel(const float* __rest
   }
 }
 
+template <bool FZ>     // (FZ: bn_bwd_apply_kernel)
 __global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* __restrict__ dy, const float* __restrict__ y_raw,
                                                             const float* __restrict__ save, const float* __restrict__ gamma,
                                                             const float* __restrict__ partial, float* __restrict__ dyr,
@@ -433,7 +456,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* __restr
           const float z = fmaf(a[j], sc, sh);
           const float dz = d[j] * (z > 0.f ? 1.f : slope);
           const float xh = (a[j] - mean) * invstd;
-          o[j] = gi * (dz - m1 - xh * m2);
+          o[j] = FZ ? gi * dz : gi * (dz - m1 - xh * m2);
         }
         *reinterpret_cast<float4*>(dyr + off[u]) = float4{o[0], o[1], o[2], o[3]};
       }
@@ -441,7 +464,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* __restr
   }
   if (t == 0 && ch == 0) {
     if (dgamma) { dgamma[c] = s2; dbeta[c] = s1; }
-    if (dbias) dbias[c] = -gi * m2 * s3;             // = the sum of dy_raw over the batch (as the clip kernels' EP_DGRAD_BN writes it)
+    // = the sum of dy_raw over the batch (as the clip kernels' EP_DGRAD_BN writes it; FZ: dy_raw = gi * dz)
+    if (dbias) dbias[c] = FZ ? gi * s1 : -gi * m2 * s3;
   }
 }
 
@@ -450,7 +474,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* __restr
 // `y` != NULL: the block's OUTPUT stands in for y_raw wherever the BatchNorm + LeakyReLU map inverts safely (conv16.h:
 // bn_inv_unsafe, evaluated on the channel's save values exactly as the forward kernels do): z = y > 0 ? y : y / slope, x_hat =
 // (z - beta) / gamma.  The in-launch forward forms (chain32 / clip32) then write y_raw only for the channels that fail the test.
-template <int NE>
+// FZ (frozen BatchNorm: `save` holds the running statistics): dy_raw = gamma*invstd*dz, without the two mean terms; y_raw is always
+// read (nothing is inverted from y); one statistics group.
+template <int NE, bool FZ = false>
 __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const float* __restrict__ dy, const float* __restrict__ y_raw,
                                                            const float* __restrict__ y, const float* __restrict__ save,
                                                            const float* __restrict__ gamma,
@@ -469,7 +495,7 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const float* __restri
   // every load is issued before the first one is consumed (clamped indices instead of branches): the kernel pays one
   // memory round trip, not NE of them -- with one wave per SIMD nothing else hides that latency
   const float mean = save[c], invstd = save[C + c], sc = save[2 * C + c], sh = save[3 * C + c], gm = gamma[c];
-  const bool from_y = y != nullptr && !bn_inv_unsafe(mean, invstd, sc, sh, slope);       // (uniform: one channel per workgroup)
+  const bool from_y = !FZ && y != nullptr && !bn_inv_unsafe(mean, invstd, sc, sh, slope);       // (uniform: one channel per workgroup)
   const float* src = from_y ? y : y_raw;
   float ry[NE], rg[NE];
   size_t ofs[NE];
@@ -509,7 +535,7 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const float* __restri
 #pragma unroll
   for (int i = 0; i < NE; ++i) {
     if (t + i * 256 < n) {
-      const float v = gi * (dz[i] - m1 - xh[i] * m2);
+      const float v = FZ ? gi * dz[i] : gi * (dz[i] - m1 - xh[i] * m2);
       dyr[ofs[i]] = v;
       cs += v;
     }
@@ -524,7 +550,7 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const float* __restri
 }
 
 // The same for rows of HW % 4 == 0 values: NV 16-byte vectors of dy and of y_raw per thread (channels of <= 1024 * NV values).
-template <int NV>
+template <int NV, bool FZ = false>
 __global__ __launch_bounds__(256) void bn_bwd_fused4_kernel(const float* __restrict__ dy, const float* __restrict__ y_raw,
                                                             const float* __restrict__ y, const float* __restrict__ save,
                                                             const float* __restrict__ gamma,
@@ -539,7 +565,7 @@ __global__ __launch_bounds__(256) void bn_bwd_fused4_kernel(const float* __restr
   for (int grp = 0; grp < sg; ++grp, save += 4 * C, dy += (size_t)B * C * HW, dyr += (size_t)B * C * HW,
            y_raw += (size_t)B * C * HW, y = y ? y + (size_t)B * C * HW : y) {
   const float mean = save[c], invstd = save[C + c], sc = save[2 * C + c], sh = save[3 * C + c], gm = gamma[c];
-  const bool from_y = y != nullptr && !bn_inv_unsafe(mean, invstd, sc, sh, slope);       // (uniform: one channel per workgroup)
+  const bool from_y = !FZ && y != nullptr && !bn_inv_unsafe(mean, invstd, sc, sh, slope);       // (uniform: one channel per workgroup)
   const float* src = from_y ? y : y_raw;
   float4 ry[NV], rg[NV];
   size_t ofs[NV];
@@ -585,7 +611,7 @@ __global__ __launch_bounds__(256) void bn_bwd_fused4_kernel(const float* __restr
     if (t + i * 256 < nv) {
       float o[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { o[j] = gi * (dz[i][j] - m1 - xh[i][j] * m2); cs += o[j]; }
+      for (int j = 0; j < 4; ++j) { o[j] = FZ ? gi * dz[i][j] : gi * (dz[i][j] - m1 - xh[i][j] * m2); cs += o[j]; }
       *reinterpret_cast<float4*>(dyr + ofs[i]) = float4{o[0], o[1], o[2], o[3]};
     }
   }
@@ -1325,7 +1351,19 @@ int launch_bn_apply(const float* y_raw, float* y, const float* save, int C, int 
   if (blocks < 1) blocks = 1;
   TimingScope ts(s, 0, 8.0 * total, "bn_apply C%d HW%d n%zu", C, HW, total);
   if (ts.skip()) return 0;
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks), dim3(256), 0, s, y_raw, y, save, C, HW, total, slope);
+  hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(blocks), dim3(256), 0, s, y_raw, y, const_cast<float*>(save), C, HW, total, slope,
+                     nullptr, nullptr, nullptr, nullptr, 0.f);
+  return check_launch("bn_apply_kernel");
+}
+
+int launch_bn_apply_frozen(const float* y_raw, float* y, float* save, const float* gamma, const float* beta, const float* rm,
+                           const float* rv, float eps, int C, int HW, size_t total, float slope, hipStream_t s) {
+  const size_t work = (HW & 3) == 0 ? total / 4 : total;       // (>= C either way: the grid's first C threads write `save`)
+  int blocks = (int)std::min<size_t>((work + 255) / 256, 4096);
+  if (blocks < 1) blocks = 1;
+  TimingScope ts(s, 0, 8.0 * total, "bn_apply C%d HW%d n%zu frozen", C, HW, total);
+  if (ts.skip()) return 0;
+  hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(blocks), dim3(256), 0, s, y_raw, y, save, C, HW, total, slope, gamma, beta, rm, rv, eps);
   return check_launch("bn_apply_kernel");
 }
 
@@ -1339,10 +1377,17 @@ int bwd_chunks(int B, int C, int* b_per_chunk) {
 }
 
 // returns 1 if the fused single-launch form was used (dbias already final, no colsum_finalize needed)
+// frozen: `save` holds the running statistics (launch_bn_apply_frozen) -- the same forms, without the batch-statistics terms
+#define MS_BN_BWD_FUSED(KERNEL, N)                                                                                                \
+  do {                                                                                                                            \
+    if (frozen) hipLaunchKernelGGL((KERNEL<N, true>), dim3(C), dim3(256), 0, s, dy, y_raw, y, save, gamma, dyr, dbias, dgamma, dbeta, B, C, HW, slope, sg); \
+    else hipLaunchKernelGGL((KERNEL<N, false>), dim3(C), dim3(256), 0, s, dy, y_raw, y, save, gamma, dyr, dbias, dgamma, dbeta, B, C, HW, slope, sg);       \
+  } while (0)
 int launch_bn_bwd(const float* dy, const float* y_raw, const float* y, const float* save, const float* gamma, float* partial, float* dyr,
                   float* colpart, float* dbias, float* dgamma, float* dbeta, int B, int C, int HW, float slope, int* fused,
-                  hipStream_t s, int sg) {
+                  hipStream_t s, int sg, bool frozen) {
   *fused = 0;
+  if (frozen) { sg = 1; y = nullptr; }      // (no statistics groups: a plain batch of B; y_raw is kept, nothing is inverted from y)
   if (sg > 1) B /= sg;                 // MS_DT_STAT_PAIR: clips per statistics group (the fused one-launch form only)
   const long n = (long)B * HW;
   if (sg > 1 && n > BN_BWD32_FUSED_MAX) return set_error("bn_bwd: statistics groups need the one-launch form (%ld values per channel)", n);
@@ -1350,43 +1395,47 @@ int launch_bn_bwd(const float* dy, const float* y_raw, const float* y, const flo
     const bool vec4 = (HW & 3) == 0 && (((uintptr_t)dy | (uintptr_t)y_raw | (uintptr_t)y | (uintptr_t)dyr) & 15) == 0;
     // (the label names the kernel's form: "4" = the 16-byte kernel, <n> its template argument)
     const int ne = vec4 ? (n <= 1024 ? 1 : n <= 2048 ? 2 : 4) : (n <= 256 * 4 ? 4 : n <= 256 * 8 ? 8 : 16);
-    TimingScope ts(s, 0, 12.0 * sg * B * C * HW, "bn_bwd_fused%s<%d> C%d HW%d B%d%s", vec4 ? "4" : "", ne, C, HW, B * sg, sg > 1 ? " pair" : "");
+    TimingScope ts(s, 0, 12.0 * sg * B * C * HW, "bn_bwd_fused%s<%d> C%d HW%d B%d%s", vec4 ? "4" : "", ne, C, HW, B * sg,
+                   frozen ? " frozen" : sg > 1 ? " pair" : "");
     if (ts.skip()) { *fused = 1; return 0; }
-    if (vec4 && n <= 1024)
-      hipLaunchKernelGGL(bn_bwd_fused4_kernel<1>, dim3(C), dim3(256), 0, s, dy, y_raw, y, save, gamma, dyr, dbias, dgamma, dbeta, B, C, HW, slope, sg);
-    else if (vec4 && n <= 2048)
-      hipLaunchKernelGGL(bn_bwd_fused4_kernel<2>, dim3(C), dim3(256), 0, s, dy, y_raw, y, save, gamma, dyr, dbias, dgamma, dbeta, B, C, HW, slope, sg);
-    else if (vec4)
-      hipLaunchKernelGGL(bn_bwd_fused4_kernel<4>, dim3(C), dim3(256), 0, s, dy, y_raw, y, save, gamma, dyr, dbias, dgamma, dbeta, B, C, HW, slope, sg);
-    else if (n <= 256 * 4)
-      hipLaunchKernelGGL(bn_bwd_fused_kernel<4>, dim3(C), dim3(256), 0, s, dy, y_raw, y, save, gamma, dyr, dbias, dgamma, dbeta, B, C, HW, slope, sg);
-    else if (n <= 256 * 8)
-      hipLaunchKernelGGL(bn_bwd_fused_kernel<8>, dim3(C), dim3(256), 0, s, dy, y_raw, y, save, gamma, dyr, dbias, dgamma, dbeta, B, C, HW, slope, sg);
-    else
-      hipLaunchKernelGGL(bn_bwd_fused_kernel<16>, dim3(C), dim3(256), 0, s, dy, y_raw, y, save, gamma, dyr, dbias, dgamma, dbeta, B, C, HW, slope, sg);
+    if (vec4 && n <= 1024) MS_BN_BWD_FUSED(bn_bwd_fused4_kernel, 1);
+    else if (vec4 && n <= 2048) MS_BN_BWD_FUSED(bn_bwd_fused4_kernel, 2);
+    else if (vec4) MS_BN_BWD_FUSED(bn_bwd_fused4_kernel, 4);
+    else if (n <= 256 * 4) MS_BN_BWD_FUSED(bn_bwd_fused_kernel, 4);
+    else if (n <= 256 * 8) MS_BN_BWD_FUSED(bn_bwd_fused_kernel, 8);
+    else MS_BN_BWD_FUSED(bn_bwd_fused_kernel, 16);
     *fused = 1;
     return check_launch("bn_bwd_fused_kernel");
   }
   int bpc;
   const int nchunk = bwd_chunks(B, C, &bpc);
   const bool vec = (HW & 3) == 0 && (((uintptr_t)dy | (uintptr_t)y_raw | (uintptr_t)dyr) & 15) == 0;
-  TimingScope ts(s, 0, 20.0 * B * C * HW, "bn_bwd(%s) C%d HW%d B%d", vec ? "reduce4+apply4" : "reduce+apply", C, HW, B);
+  TimingScope ts(s, 0, 20.0 * B * C * HW, "bn_bwd(%s) C%d HW%d B%d%s", vec ? "reduce4+apply4" : "reduce+apply", C, HW, B, frozen ? " frozen" : "");
   if (ts.skip()) return 0;
+  // (the reduce pass is the train form's as it is: the sums of dz and dz * x_hat are dbeta and dgamma in either form)
   if (vec) hipLaunchKernelGGL(bn_bwd_reduce4_kernel, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, partial, colpart, B, C, HW, bpc, slope);
   else hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, partial, B, C, HW, bpc, slope);
   int rc = check_launch("bn_bwd_reduce_kernel");
   if (rc) return rc;
   if (vec) {
     // (the 16-byte form writes the bias gradient itself: *fused = 1 tells the caller that no colsum_finalize launch is needed)
-    hipLaunchKernelGGL(bn_bwd_apply4_kernel, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, partial, dyr, colpart, dbias,
-                       dgamma, dbeta, B, C, HW, bpc, slope);
+    if (frozen)
+      hipLaunchKernelGGL(bn_bwd_apply4_kernel<true>, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, partial, dyr, colpart, dbias,
+                         dgamma, dbeta, B, C, HW, bpc, slope);
+    else
+      hipLaunchKernelGGL(bn_bwd_apply4_kernel<false>, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, partial, dyr, colpart, dbias,
+                         dgamma, dbeta, B, C, HW, bpc, slope);
     *fused = 1;
+  } else if (frozen) {
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, partial, dyr, colpart,
+                       dgamma, dbeta, B, C, HW, bpc, slope);
   } else {
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, partial, dyr, colpart,
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, partial, dyr, colpart,
                        dgamma, dbeta, B, C, HW, bpc, slope);
   }
   return check_launch("bn_bwd_apply_kernel");
 }
+#undef MS_BN_BWD_FUSED
 
 // returns 1 in *fused when the bias gradient was written by this launch (no colsum_finalize needed)
 int launch_act_bwd(const float* dy, const float* y, float* dyr, float* colpart, float* dbias, int B, int C, int HW, int mode, float slope,

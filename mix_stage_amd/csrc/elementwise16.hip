@@ -9,13 +9,26 @@
 namespace ms {
 
 // y = lrelu(y_raw * scale[c] + shift[c]); y cb8, or plain fp32 (B, C, HW) when y_f32 != NULL
-template <typename DT>
+// FZ (frozen BatchNorm, the differentiable BN_EVAL block): scale / shift from the running statistics in fp32 (frozen_bn, kernels.h),
+// derived by every thread for its 8 channels; the grid's first C threads write `save` for the backward pass
+template <typename DT, bool FZ>
 __global__ __launch_bounds__(256) void bn_apply16_kernel(const u32x4* __restrict__ y_raw, u32x4* __restrict__ y,
-                                                         float* __restrict__ y_f32, const float* __restrict__ save, int C,
-                                                         int C8, int HW, size_t total, float slope) {
+                                                         float* __restrict__ y_f32, float* __restrict__ save, int C,
+                                                         int C8, int HW, size_t total, float slope, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, const float* __restrict__ rm,
+                                                         const float* __restrict__ rv, float eps) {
   prefetch_kernargs<192>();
   const float* scale = save + 2 * (size_t)C;
   const float* shift = save + 3 * (size_t)C;
+  if (FZ) {
+    for (size_t c = (size_t)blockIdx.x * 256 + threadIdx.x; c < (size_t)C; c += (size_t)gridDim.x * 256) {
+      const FrozenBN f = frozen_bn(gamma, beta, rm, rv, eps, (int)c);
+      save[c] = f.mean;
+      save[C + c] = f.invstd;
+      save[2 * (size_t)C + c] = f.sc;
+      save[3 * (size_t)C + c] = f.sh;
+    }
+  }
   for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < total; v += (size_t)gridDim.x * 256) {
     const size_t bc = v / HW;
     const int cb = (int)(bc % C8), pix = (int)(v - bc * HW);
@@ -25,7 +38,12 @@ __global__ __launch_bounds__(256) void bn_apply16_kernel(const u32x4* __restrict
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int c = cb * 8 + j;
-      f[j] = c < C ? lrelu(fmaf(f[j], scale[c], shift[c]), slope) : 0.f;
+      if (FZ) {
+        const FrozenBN fz = frozen_bn(gamma, beta, rm, rv, eps, min(c, C - 1));
+        f[j] = c < C ? lrelu(fmaf(f[j], fz.sc, fz.sh), slope) : 0.f;
+      } else {
+        f[j] = c < C ? lrelu(fmaf(f[j], scale[c], shift[c]), slope) : 0.f;
+      }
     }
     if (y_f32) {
 #pragma unroll
@@ -45,11 +63,28 @@ int launch_bn_apply16(int dt, const void* y_raw, void* y, float* y_f32, const fl
   TimingScope ts(s, 0, (y_f32 ? 2.0 + 4.0 : 4.0) * 8.0 * total, "bn_apply16_kernel|bn_apply16 C%d N%d", C, B * HW);
   if (ts.skip()) return 0;
   if (dt == DT_BF16)
-    hipLaunchKernelGGL(bn_apply16_kernel<BF16>, dim3(blocks), dim3(256), 0, s, (const u32x4*)y_raw, (u32x4*)y, y_f32, save, C, C8, HW,
-                       total, slope);
+    hipLaunchKernelGGL((bn_apply16_kernel<BF16, false>), dim3(blocks), dim3(256), 0, s, (const u32x4*)y_raw, (u32x4*)y, y_f32,
+                       const_cast<float*>(save), C, C8, HW, total, slope, nullptr, nullptr, nullptr, nullptr, 0.f);
   else
-    hipLaunchKernelGGL(bn_apply16_kernel<F16>, dim3(blocks), dim3(256), 0, s, (const u32x4*)y_raw, (u32x4*)y, y_f32, save, C, C8, HW,
-                       total, slope);
+    hipLaunchKernelGGL((bn_apply16_kernel<F16, false>), dim3(blocks), dim3(256), 0, s, (const u32x4*)y_raw, (u32x4*)y, y_f32,
+                       const_cast<float*>(save), C, C8, HW, total, slope, nullptr, nullptr, nullptr, nullptr, 0.f);
+  return check_launch("bn_apply16_kernel");
+}
+
+int launch_bn_apply16_frozen(int dt, const void* y_raw, void* y, float* y_f32, float* save, const float* gamma, const float* beta,
+                             const float* rm, const float* rv, float eps, int B, int C, int HW, float slope, hipStream_t s) {
+  const int C8 = c8_of(C);
+  const size_t total = (size_t)B * C8 * HW;
+  // (the grid's first C threads write `save`: at least C8 * 8 threads' worth of workgroups, whatever the tensor's size)
+  const int blocks = (int)std::min<size_t>(std::max<size_t>((total + 255) / 256, (size_t)(C + 255) / 256), 8192);
+  TimingScope ts(s, 0, (y_f32 ? 2.0 + 4.0 : 4.0) * 8.0 * total, "bn_apply16_kernel|bn_apply16 C%d N%d frozen", C, B * HW);
+  if (ts.skip()) return 0;
+  if (dt == DT_BF16)
+    hipLaunchKernelGGL((bn_apply16_kernel<BF16, true>), dim3(blocks), dim3(256), 0, s, (const u32x4*)y_raw, (u32x4*)y, y_f32, save, C, C8,
+                       HW, total, slope, gamma, beta, rm, rv, eps);
+  else
+    hipLaunchKernelGGL((bn_apply16_kernel<F16, true>), dim3(blocks), dim3(256), 0, s, (const u32x4*)y_raw, (u32x4*)y, y_f32, save, C, C8,
+                       HW, total, slope, gamma, beta, rm, rv, eps);
   return check_launch("bn_apply16_kernel");
 }
 
@@ -397,7 +432,8 @@ __global__ __launch_bounds__(256) void bn_bwd16_reduce_kernel(const u32x4* __res
 }
 
 //   pass 2: dyr = gamma*invstd*(dz - s1/N - xh*s2/N); colsum partial of dyr; dgamma = s2, dbeta = s1
-template <typename DT, bool DYF32>
+// FZ (frozen BatchNorm: `save` holds the running statistics): dyr = gamma*invstd*dz, without the two batch-mean terms
+template <typename DT, bool DYF32, bool FZ>
 __global__ __launch_bounds__(256) void bn_bwd16_apply_kernel(const u32x4* __restrict__ dy, const float* __restrict__ dy_f32,
                                                              const u32x4* __restrict__ y_raw, const u32x4* __restrict__ y_out,
                                                              const float* __restrict__ save,
@@ -437,7 +473,8 @@ __global__ __launch_bounds__(256) void bn_bwd16_apply_kernel(const u32x4* __rest
   }
   if (t < 8 && ch == 0 && cb * 8 + t < C) {
     if (dgamma) { dgamma[cb * 8 + t] = prm[48 + t]; dbeta[cb * 8 + t] = prm[40 + t]; }
-    if (dbias) dbias[cb * 8 + t] = -(prm[32 + t] * prm[8 + t]) * (prm[48 + t] * invN) * prm[56 + t];      // sum of dy_raw over the batch
+    // sum of dy_raw over the batch (FZ: dy_raw = gamma invstd dz)
+    if (dbias) dbias[cb * 8 + t] = FZ ? (prm[32 + t] * prm[8 + t]) * prm[40 + t] : -(prm[32 + t] * prm[8 + t]) * (prm[48 + t] * invN) * prm[56 + t];
   }
   // chunk = b_per_chunk consecutive vectors of this channel block's flattened (batch item, pixel) space
   const int e_base = ch * b_per_chunk, b0 = 0;
@@ -476,7 +513,7 @@ __global__ __launch_bounds__(256) void bn_bwd16_apply_kernel(const u32x4* __rest
           float xh; bool pos;
           bn_xhat_mask(ks[j], yr[j], xh, pos);
           const float dz = g[j] * (pos ? 1.f : slope);
-          o[j] = gi[j] * (dz - m1[j] - xh * m2[j]);
+          o[j] = FZ ? gi[j] * dz : gi[j] * (dz - m1[j] - xh * m2[j]);
         }
         dyr[vofs[q]] = pack8<DT>(o);
       }
@@ -487,7 +524,8 @@ __global__ __launch_bounds__(256) void bn_bwd16_apply_kernel(const u32x4* __rest
 // Fused form for channel blocks with <= 256*NE vectors (every 1-D layer of the path at B*T <= 2048): one workgroup owns a
 // channel block, keeps dz / x_hat in registers across the reduction and writes dy_raw, dgamma, dbeta and the bias gradient
 // in ONE launch.
-template <typename DT, bool DYF32, int NE, int NT>
+// FZ: as bn_bwd16_apply_kernel (one statistics group, y_out == NULL: y_raw is kept whole and always read)
+template <typename DT, bool DYF32, int NE, int NT, bool FZ>
 __global__ __launch_bounds__(NT) void bn_bwd16_fused_kernel(const u32x4* __restrict__ dy, const float* __restrict__ dy_f32,
                                                              const u32x4* __restrict__ y_raw, const u32x4* __restrict__ y_out,
                                                              const float* __restrict__ save,
@@ -575,7 +613,7 @@ __global__ __launch_bounds__(NT) void bn_bwd16_fused_kernel(const u32x4* __restr
     float o[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      o[j] = gi[j] * (dz[i][j] - s12[j] * invN - xh[i][j] * (s12[8 + j] * invN));
+      o[j] = FZ ? gi[j] * dz[i][j] : gi[j] * (dz[i][j] - s12[j] * invN - xh[i][j] * (s12[8 + j] * invN));
       cs[j] += t + i * NT < n ? o[j] : 0.f;
     }
     if (t + i * NT < n) dyr[vofs[i]] = pack8<DT>(o);
@@ -611,9 +649,10 @@ int bwd16_chunks(int B, int C8, int HW, int* b_per_chunk) {
 
 int launch_bn_bwd16(int dt, const void* dy, const float* dy_f32, const void* y_raw, const void* y, const float* save, const float* gamma,
                     float* partial, void* dyr, float* colpart, float* dbias, float* dgamma, float* dbeta, int B, int C, int HW,
-                    float slope, int* bias_done, hipStream_t s, int sg) {
+                    float slope, int* bias_done, hipStream_t s, int sg, bool frozen) {
   const int C8 = c8_of(C);
   *bias_done = 0;
+  if (frozen) { sg = 1; y = nullptr; }   // (no statistics groups: a plain batch of B; nothing is inverted from y)
   if (sg > 1) B /= sg;                  // MS_DT_STAT_PAIR: clips per statistics group (the one-launch form only)
   if (sg > 1 && (long)B * HW > BN_BWD16_FUSED_MAX) return set_error("bn_bwd16: statistics groups need the one-launch form");
   if ((long)B * HW <= BN_BWD16_FUSED_MAX) {
@@ -622,11 +661,15 @@ int launch_bn_bwd16(int dt, const void* dy, const float* dy_f32, const void* y_r
     const int n = B * HW;
     const int nt = 256;       // (1024-thread workgroups measured 2x slower here: 29 vs 15 us at C = 256, B*T = 2048)
     const int ne = (n + nt - 1) / nt;
-    TimingScope ts(s, 0, 16.0 * (dy_f32 ? 4.0 + 1.0 + 1.0 : 3.0) * (double)B * C8 * HW, "bn_bwd16_fused_kernel|bn_bwd16 C%d N%d fused", C, B * HW);
+    TimingScope ts(s, 0, 16.0 * (dy_f32 ? 4.0 + 1.0 + 1.0 : 3.0) * (double)B * C8 * HW, "bn_bwd16_fused_kernel|bn_bwd16 C%d N%d fused%s", C, B * HW, frozen ? " frozen" : "");
     if (ts.skip()) return 0;
 #define MS_BNF(DT, F, NE, NT)                                                                                                      \
-    hipLaunchKernelGGL((bn_bwd16_fused_kernel<DT, F, NE, NT>), dim3(C8), dim3(NT), 0, s, (const u32x4*)dy, dy_f32, (const u32x4*)y_raw, \
-                       (const u32x4*)y, save, gamma, (u32x4*)dyr, dbias, dgamma, dbeta, B, C, C8, HW, slope, sg)
+    do {                                                                                                                           \
+      if (frozen) hipLaunchKernelGGL((bn_bwd16_fused_kernel<DT, F, NE, NT, true>), dim3(C8), dim3(NT), 0, s, (const u32x4*)dy, dy_f32, (const u32x4*)y_raw, \
+                                     (const u32x4*)y, save, gamma, (u32x4*)dyr, dbias, dgamma, dbeta, B, C, C8, HW, slope, sg);     \
+      else hipLaunchKernelGGL((bn_bwd16_fused_kernel<DT, F, NE, NT, false>), dim3(C8), dim3(NT), 0, s, (const u32x4*)dy, dy_f32, (const u32x4*)y_raw, \
+                              (const u32x4*)y, save, gamma, (u32x4*)dyr, dbias, dgamma, dbeta, B, C, C8, HW, slope, sg);            \
+    } while (0)
 #define MS_BNF_NE(DT, F) do { if (ne <= 1) MS_BNF(DT, F, 1, 256); else if (ne <= 2) MS_BNF(DT, F, 2, 256);                         \
                               else if (ne <= 4) MS_BNF(DT, F, 4, 256); else MS_BNF(DT, F, 8, 256); } while (0)
     if (dt == DT_BF16) { if (dy_f32) MS_BNF_NE(BF16, true); else MS_BNF_NE(BF16, false); }
@@ -639,13 +682,16 @@ int launch_bn_bwd16(int dt, const void* dy, const float* dy_f32, const void* y_r
   const int nchunk = bwd16_chunks(B, C8, HW, &bpc);
   const dim3 grid(C8, nchunk);
   const double vec = (double)B * C8 * HW;
-  TimingScope ts(s, 0, 16.0 * (dy_f32 ? 4.0 + 2.0 + 1.0 : 5.0) * vec, "bn_bwd16_kernels|bn_bwd16 C%d N%d", C, B * HW);
+  TimingScope ts(s, 0, 16.0 * (dy_f32 ? 4.0 + 2.0 + 1.0 : 5.0) * vec, "bn_bwd16_kernels|bn_bwd16 C%d N%d%s", C, B * HW, frozen ? " frozen" : "");
   if (ts.skip()) return 0;
 #define MS_BNB(DT, F)                                                                                                              \
   do {                                                                                                                             \
     hipLaunchKernelGGL((bn_bwd16_reduce_kernel<DT, F>), grid, dim3(256), 0, s, (const u32x4*)dy, dy_f32, (const u32x4*)y_raw,         \
                        (const u32x4*)y, save, partial, colpart, B, C, C8, HW, bpc, slope);                                         \
-    hipLaunchKernelGGL((bn_bwd16_apply_kernel<DT, F>), grid, dim3(256), 0, s, (const u32x4*)dy, dy_f32, (const u32x4*)y_raw,          \
+    if (frozen) hipLaunchKernelGGL((bn_bwd16_apply_kernel<DT, F, true>), grid, dim3(256), 0, s, (const u32x4*)dy, dy_f32, (const u32x4*)y_raw, \
+                       (const u32x4*)y, save,                                                                                      \
+                       gamma, partial, (u32x4*)dyr, colpart, dbias, dgamma, dbeta, B, C, C8, HW, bpc, slope);                      \
+    else hipLaunchKernelGGL((bn_bwd16_apply_kernel<DT, F, false>), grid, dim3(256), 0, s, (const u32x4*)dy, dy_f32, (const u32x4*)y_raw, \
                        (const u32x4*)y, save,                                                                                      \
                        gamma, partial, (u32x4*)dyr, colpart, dbias, dgamma, dbeta, B, C, C8, HW, bpc, slope);                      \
   } while (0)

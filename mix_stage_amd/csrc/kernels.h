@@ -278,7 +278,24 @@ int launch_transpose_weight(const float* w, float* wt, int groups, int Cog, int 
 size_t dgrad_weight_elems(int groups, int Cog, int Cig, int KH, int KW, int SH, int SW);
 int launch_bn_finalize(const float* stats, const float* counts, int n_tiles, int tile_n, int N, int C, const float* gamma,
                        const float* beta, float* rm, float* rv, float* save, float eps, float momentum, hipStream_t s);
+// mean | invstd | scale | shift of channel c from the RUNNING statistics, in fp32 with the operations of bn_finalize_kernel's last
+// step (frozen BatchNorm: the statistics are read, never written)
+struct FrozenBN { float mean, invstd, sc, sh; };
+__device__ __forceinline__ FrozenBN frozen_bn(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                              const float* __restrict__ rm, const float* __restrict__ rv, float eps, int c) {
+  FrozenBN f;
+  f.mean = rm[c];
+  f.invstd = 1.0f / sqrtf(rv[c] + eps);
+  f.sc = gamma[c] * f.invstd;
+  f.sh = fmaf(-f.mean, f.sc, beta[c]);
+  return f;
+}
+
 int launch_bn_apply(const float* y_raw, float* y, const float* save, int C, int HW, size_t total, float slope, hipStream_t s);
+// frozen BatchNorm (a differentiable MS_BN_EVAL block): `save` = mean | invstd | scale | shift WRITTEN from the running statistics
+// by the same launch that normalises and activates
+int launch_bn_apply_frozen(const float* y_raw, float* y, float* save, const float* gamma, const float* beta, const float* rm,
+                           const float* rv, float eps, int C, int HW, size_t total, float slope, hipStream_t s);
 int launch_bn_finalize_apply(const float* stats, const float* counts, int n_tiles, int tile_n, int N, int C, const float* gamma,
                              const float* beta, float* rm, float* rv, float* save, float eps, float momentum, const float* y_raw,
                              float* y, int B, int HW, float slope, hipStream_t s);
@@ -288,7 +305,7 @@ int bwd_chunks(int B, int C, int* b_per_chunk);
 constexpr int BN_BWD32_FUSED_MAX = 256 * 16;
 int launch_bn_bwd(const float* dy, const float* y_raw, const float* y, const float* save, const float* gamma, float* partial, float* dyr,
                   float* colpart, float* dbias, float* dgamma, float* dbeta, int B, int C, int HW, float slope, int* fused,
-                  hipStream_t s, int sg = 1);
+                  hipStream_t s, int sg = 1, bool frozen = false);
 int launch_act_bwd(const float* dy, const float* y, float* dyr, float* colpart, float* dbias, int B, int C, int HW, int mode, float slope, int* fused,
                    hipStream_t s);
 int launch_colsum_finalize(const float* colpart, float* out, int B, int C, hipStream_t s);

@@ -45,6 +45,54 @@ def compute_dtype(module):
   return getattr(module, '_ms_dt', 0)
 
 
+def freeze_batchnorm(root, frozen=True):
+  """Frozen BatchNorm statistics for every ConvNormRelu under `root` (fine-tuning a checkpoint): a flagged block normalises with
+  its running statistics whatever its `training` flag says, never moves them or num_batches_tracked, and can be differentiated --
+  what nn.BatchNorm*.eval() does under autograd; the affine parameters stay trainable unless their requires_grad is off.
+  `_bn_frozen` is a plain attribute (copy.deepcopy carries it, the state_dict does not).  -> the number of blocks flagged."""
+  n = 0
+  for m in root.modules():
+    if isinstance(m, ConvNormRelu):
+      m._bn_frozen = bool(frozen)
+      n += 1
+  return n
+
+
+def freeze_bn_roots(model, freeze_bn):
+  """The modules MixStageTrainStep(freeze_bn=) names: None -> none, True -> the model, 'G' / 'D' -> that network, or an iterable of
+  modules of the model and dotted names under it.  Anything else is a ValueError."""
+  if freeze_bn is None or freeze_bn is False:
+    return []
+  if freeze_bn is True:
+    return [model]
+  if isinstance(freeze_bn, str):
+    if freeze_bn not in ('G', 'D'):
+      raise ValueError("freeze_bn: %r is not 'G' or 'D' (dotted names go in a list)" % (freeze_bn,))
+    return [getattr(model, freeze_bn)]
+  if isinstance(freeze_bn, nn.Module) or not hasattr(freeze_bn, '__iter__'):
+    raise ValueError('freeze_bn must be None, True, \'G\', \'D\' or an iterable of modules / dotted names, got %r' % type(freeze_bn).__name__)
+  named = dict(model.named_modules())
+  inside = set(id(m) for m in named.values())
+  roots = []
+  for item in freeze_bn:
+    if isinstance(item, str):
+      if item not in named:
+        raise ValueError('freeze_bn: the model has no sub-module %r' % item)
+      roots.append(named[item])
+    elif isinstance(item, nn.Module):
+      if id(item) not in inside:
+        raise ValueError('freeze_bn: a %s that is not a module of the model' % type(item).__name__)
+      roots.append(item)
+    else:
+      raise ValueError('freeze_bn: an entry of type %s (modules or dotted names)' % type(item).__name__)
+  return roots
+
+
+def frozen_batchnorm_blocks(root):
+  """The ConvNormRelu blocks under `root` that freeze_batchnorm flagged."""
+  return [m for m in root.modules() if isinstance(m, ConvNormRelu) and getattr(m, '_bn_frozen', False)]
+
+
 # set to a list while a training step is being graph-captured: the ConvNormRelu blocks that ran with batch
 # statistics are recorded so graph replays can keep their num_batches_tracked counts right (train_step.py)
 _train_tape = None
@@ -159,7 +207,8 @@ class ConvNormRelu(nn.Module):
     if self._p and self.training:
       raise NotImplementedError('dropout p>0 is not on the Mix-StAGE path (p=0 everywhere, JL:26)')
     n = self.norm
-    if self.training and n.track_running_stats:
+    frozen = bool(getattr(self, '_bn_frozen', False))
+    if self.training and n.track_running_stats and not frozen:
       mode = MS_BN_TRAIN
       self._note_train_pass()
       if ops.stat_pair_active():
@@ -184,7 +233,7 @@ class ConvNormRelu(nn.Module):
         return y if (was_plain or out_f32) else ops16.to_cb8(y, dt)
       y = ops16.conv_block16(x, self.conv.weight, self.conv.bias, self._geometry(), mode, n.weight, n.bias, n.running_mean,
                              n.running_var, x2=x2, in_mode=in_mode, out_f32=out_f32,
-                             bn_folded=getattr(self, '_bn_folded', False), link=link)
+                             bn_folded=getattr(self, '_bn_folded', False), link=link, frozen=frozen)
       return ops16.from_cb8(y, self.conv.weight.shape[0]) if (was_plain and not out_f32) else y
     if mode == MS_BN_TRAIN and ops.bn_sync_active():
       # data parallel with bn_sync='global': bare conv, then BatchNorm over the batch of ALL ranks (two small collectives)
@@ -192,17 +241,20 @@ class ConvNormRelu(nn.Module):
       y_raw = ops.conv_block(x, self.conv.weight, self.conv.bias, g, MS_BARE, x2=x2, in_mode=in_mode)
       return ops.sync_bn_act(y_raw, n.weight, n.bias, n.running_mean, n.running_var, g.slope, g.eps, g.momentum)
     return ops.conv_block(x, self.conv.weight, self.conv.bias, self._geometry(), mode, n.weight, n.bias,
-                          n.running_mean, n.running_var, x2=x2, in_mode=in_mode, chain_prev=chain_prev and mode == MS_BN_TRAIN,
-                          link=link)
+                          n.running_mean, n.running_var, x2=x2, in_mode=in_mode,
+                          chain_prev=chain_prev and (mode == MS_BN_TRAIN or frozen), link=link, frozen=frozen)
 
   def _next_desc(self, x):
     """The descriptor the fp32 block would run on the plain input x (ops.corun plans with it), None where that is not one launch."""
     n = self.norm
     if self._nd != 1 or getattr(self, '_ms_dt', 0) or x.dim() != 3 or (self._p and self.training):
       return None
-    train = self.training and n.track_running_stats
+    frozen = bool(getattr(self, '_bn_frozen', False))
+    train = self.training and n.track_running_stats and not frozen
     if train and ops.bn_sync_active():
       return None
+    if frozen and torch.is_grad_enabled():
+      return None          # (the differentiable frozen form is two launches: no co-run hold for it)
     w = self.conv.weight
     return self._geometry().desc(x.shape[0], w.shape[1], 1, x.shape[2], w.shape[0] // self.conv.groups, MS_BN_TRAIN if train else MS_BN_EVAL,
                                  MS_IN_PLAIN, 0)

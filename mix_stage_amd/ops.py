@@ -426,7 +426,10 @@ class ResidualLink:
 
 class _ConvBlockFn(torch.autograd.Function):
   @staticmethod
-  def forward(ctx, x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, pre=None, prev=None, link=None):
+  def forward(ctx, x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, pre=None, prev=None, link=None, frozen=False):
+    # frozen: an MS_BN_EVAL block somebody differentiates (layers.freeze_batchnorm) -- the forward keeps y_raw and `save` (written
+    # from the running statistics, which are only read), the backward is the frozen form of ms_conv_block_bwd
+    frozen = bool(frozen) and mode == MS_BN_EVAL and pre is None
     rm, rv = stats if stats is not None else (None, None)
     _need_hip(x, x2, w, bias, gamma, beta, rm, rv)
     xin = x                              # (the caller's tensor: its grad_fn is the node that will read this block's dx)
@@ -447,7 +450,7 @@ class _ConvBlockFn(torch.autograd.Function):
     if in_mode == MS_IN_UP2ADD and (x.shape[2] * 2 != W or x2.shape[1] != exp_c):
       raise RuntimeError('UP2ADD: a %s and residual %s do not match' % (tuple(x.shape), tuple(x2.shape)))
     pair = MS_DT_STAT_PAIR if (_stat_pair['on'] and pre is None) else 0
-    d = geom.desc(B, Cin_g, H, W, Cout_g, mode, in_mode, pair)
+    d = geom.desc(B, Cin_g, H, W, Cout_g, mode, in_mode, pair | (_lib.MS_DT_BN_FROZEN if frozen else 0))
     oshape = (B, ctot, d.OH, d.OW) if nd == 2 else (B, ctot, d.OW)
     if pre is not None:
       # the block's results were produced by a launch that chains several blocks (decoder_chain): nothing to run here, this
@@ -458,9 +461,10 @@ class _ConvBlockFn(torch.autograd.Function):
     else:
       y = torch.empty(oshape, dtype=torch.float32, device=x.device)
       y_raw = save = None
-      if mode == MS_BN_TRAIN:
+      if mode == MS_BN_TRAIN or frozen:
         y_raw = torch.empty_like(y)
-        save = torch.empty((8 if pair else 4) * ctot, dtype=torch.float32, device=x.device)     # (one vector per statistics group)
+        # (one vector per statistics group; a frozen block has no groups)
+        save = torch.empty((8 if (pair and not frozen) else 4) * ctot, dtype=torch.float32, device=x.device)
     ws = workspace(d._fwd_ws, x.device) if pre is None else None
     planes = _prepared_for(w, d, 'fwd') if pre is None else None
     if pre is None:
@@ -479,14 +483,14 @@ class _ConvBlockFn(torch.autograd.Function):
         # without autograd nothing else holds y_raw / save / the input, and the allocator would hand them to the next taker
         _corun['keep'].append((x, x2, w, bias, gamma, beta, rm, rv, y_raw, y, save, ws, planes, sync))
     ctx.geom_desc = d
-    ctx.mode, ctx.in_mode = mode, in_mode
+    ctx.mode, ctx.in_mode, ctx.frozen = mode, in_mode, frozen
     # a block of a guest chain (corun): its node was created between the host's nodes, so autograd runs its backward between the
     # host's too, and its data gradient may wait for the next host block's launch (backward: _bwd_guest_ok).  Only where the
     # reader of that data gradient is known to pass through the hold first: x is the output of another conv block of this
     # class, whose backward flushes or takes a held launch before it reads anything, and nobody watches x (a tensor hook or
     # retain_grad() would read the gradient as soon as this block's backward returns).  The chain's first block, whose input
     # comes from a transpose, launches at once.
-    ctx.corun_guest = bool(_corun['in_guest'] and pre is None and nd == 1 and xin is not None and xin.grad_fn is not None
+    ctx.corun_guest = bool(_corun['in_guest'] and pre is None and not frozen and nd == 1 and xin is not None and xin.grad_fn is not None
                            and type(xin.grad_fn).__name__ == '_ConvBlockFnBackward'
                            and not (getattr(xin, '_backward_hooks', None) or getattr(xin, 'retains_grad', False)))
     # `prev`: the autograd node of the BN_TRAIN block that produced x, handed over by a container that knows x has no other
@@ -537,10 +541,10 @@ class _ConvBlockFn(torch.autograd.Function):
   def _backward(ctx, dy):
     x, x2, w, gamma, y_raw, y, save = ctx.saved_tensors
     d, mode, in_mode = ctx.geom_desc, ctx.mode, ctx.in_mode
-    if mode == MS_BN_EVAL:
+    if mode == MS_BN_EVAL and not ctx.frozen:
       raise RuntimeError('backward through an eval-mode (running-stats) ConvNormRelu is not on the path')
     need_x, need_x2, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-    need_bn = mode == MS_BN_TRAIN and ctx.needs_input_grad[4]
+    need_bn = (mode == MS_BN_TRAIN or ctx.frozen) and ctx.needs_input_grad[4]
     dy = dy.contiguous()
     dev = dy.device
     is_dyr = bool(ctx.dy_is_dyr)          # a consumer's fused launch already ran this block's BatchNorm + activation backward
@@ -603,7 +607,7 @@ class _ConvBlockFn(torch.autograd.Function):
       # a second contribution to a parameter in this step (autograd will add it on this stream): the first one may
       # still be in flight on the side stream
       torch.cuda.current_stream().wait_stream(side)
-    if side is not None and direct_w is True and (dbias is None or direct_b is True):
+    if side is not None and not ctx.frozen and direct_w is True and (dbias is None or direct_b is True):
       # dw goes straight into the flat gradient buffer, so nothing downstream in autograd reads it: run it on the side
       # stream.  Its inputs must outlive this function until the streams are joined.
       ws2 = side_workspace(d._bwd_ws, dev)
@@ -667,7 +671,7 @@ class _ConvBlockFn(torch.autograd.Function):
       ctx.link[0].grad = dx2                # the consumer's data-gradient launch adds it: autograd gets None for the residual
       dx2 = None
     return (dx, dx2, None if direct_w else dw, None if direct_b else dbias, None if direct_g else dgamma,
-            None if direct_be else dbeta, None, None, None, None, None, None, None)
+            None if direct_be else dbeta, None, None, None, None, None, None, None, None)
 
 
 def _f32(t):
@@ -716,15 +720,24 @@ def residual_links16_active():
   return _links16['on'] and _chain_fusion['on']
 
 
+def needs_grad(*tensors):
+  """Does autograd record an operation on these tensors right now?"""
+  return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
 def conv_block(x, w, bias, geom, mode, gamma=None, beta=None, running_mean=None, running_var=None, x2=None,
-               in_mode=MS_IN_PLAIN, chain_prev=False, link=None):
-  """One conv block of the path on the HIP kernels (see include/mixstage.h: ms_conv_block_fwd/bwd)."""
+               in_mode=MS_IN_PLAIN, chain_prev=False, link=None, frozen=False):
+  """One conv block of the path on the HIP kernels (see include/mixstage.h: ms_conv_block_fwd/bwd).
+  frozen: an MS_BN_EVAL block that may be differentiated (frozen BatchNorm statistics).  Where nothing needs a gradient it is
+  the one-launch eval form, as without the flag."""
+  frozen = bool(frozen) and mode == MS_BN_EVAL and needs_grad(x, x2, w, bias, gamma, beta)
   if w.dtype == torch.float64 or x.dtype == torch.float64:
     # .double() model: fp32 shadows of the parameters (differentiable casts) and of the running statistics, which the
     # kernels update in place and which are written back to the float64 buffers
     rm32, rv32 = _f32(running_mean), _f32(running_var)
     stats = (rm32, rv32) if rm32 is not None else None
-    y = _ConvBlockFn.apply(_f32(x), _f32(x2), _f32(w), _f32(bias), _f32(gamma), _f32(beta), geom, mode, in_mode, stats)
+    y = _ConvBlockFn.apply(_f32(x), _f32(x2), _f32(w), _f32(bias), _f32(gamma), _f32(beta), geom, mode, in_mode, stats, None, None, None,
+                           frozen)
     if mode == MS_BN_TRAIN and running_mean is not None and running_mean.dtype == torch.float64:
       with torch.no_grad():
         running_mean.copy_(rm32)
@@ -736,9 +749,10 @@ def conv_block(x, w, bias, geom, mode, gamma=None, beta=None, running_mean=None,
   link = link if (link is not None and _chain_fusion['on'] and torch.is_grad_enabled()) else None
   # a guest chain rides along (corun): its next block is planned now and shares this block's launch, or nothing happens
   drv = _corun['driver']
-  held = drv is not None and not drv.in_guest and geom.nd == 1 and drv.offer(x, x2, w, geom, mode, in_mode)
+  # (a frozen block is two launches: no co-run hold for it, as host or as guest)
+  held = drv is not None and not drv.in_guest and not frozen and geom.nd == 1 and drv.offer(x, x2, w, geom, mode, in_mode)
   if not held:
-    return _ConvBlockFn.apply(x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, None, prev, link)
+    return _ConvBlockFn.apply(x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, None, prev, link, frozen)
   try:
     y = _ConvBlockFn.apply(x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, None, prev, link)
     check(lib().ms_clip_hold_flush(_stream()), 'ms_clip_hold_flush')      # (a block this launch did not take goes now)
@@ -1089,14 +1103,16 @@ def decoder_chain(x, blocks, logits, score, P):
     return None
   if tuple(score.shape) != (B, M, T) or score.dtype != torch.float32:
     return None
-  training = all(m.training and m.norm.track_running_stats for m in blocks)
-  if not training and any(m.training for m in blocks):
+  # (a frozen block -- layers.freeze_batchnorm -- normalises with its running statistics whatever its training flag says)
+  batch_stats = [m.training and not getattr(m, '_bn_frozen', False) for m in blocks]
+  training = all(b and m.norm.track_running_stats for b, m in zip(batch_stats, blocks))
+  if not training and any(batch_stats):
     return None
   mode = MS_BN_TRAIN if training else MS_BN_EVAL
   params = [t for m in blocks for t in (m.conv.weight, m.conv.bias, m.norm.weight, m.norm.bias)] + [logits.weight, logits.bias]
   need_grad = torch.is_grad_enabled() and (x.requires_grad or score.requires_grad or any(t is not None and t.requires_grad for t in params))
   if need_grad and not training:
-    return None                            # (eval-mode blocks are never differentiated on the path)
+    return None                            # (no chained form differentiates running-statistics blocks: frozen ones run one by one)
   d = _chain_desc(B, M, T, cin0, P, mode, blk0)
   ws = [m.conv.weight for m in blocks] + [logits.weight]
   if not lib().ms_decoder_chain_supported(ctypes.byref(d)):

@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from ._lib import (BwdOptions, ConvDesc, FwdOptions, MS_BARE, MS_BF16, MS_BN_EVAL, MS_BN_TRAIN, MS_DT_BN_FOLDED, MS_DT_OUT_F32, MS_DT_STAT_PAIR,
                    MS_F16, MS_IN_BCAST, MS_IN_PLAIN, MS_IN_UP2ADD, MS_LRELU, Prep16Item, check, lib)
 from .ops import _grad_slot, _ptr, _stream, workspace
@@ -257,7 +257,12 @@ def _prepared16_for(w, d, kind, bn=None):
 # ------------------------------------------------------------------------------------------------
 class _ConvBlock16Fn(torch.autograd.Function):
   @staticmethod
-  def forward(ctx, x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, dt_flags, pre=None, link=None):
+  def forward(ctx, x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, dt_flags, pre=None, link=None, frozen=False):
+    # frozen: an MS_BN_EVAL block somebody differentiates (layers.freeze_batchnorm), as in the fp32 twin: the forward keeps y_raw
+    # (cb8) and `save` written from the running statistics, the backward is the frozen form of ms_conv_block_bwd
+    frozen = bool(frozen) and mode == MS_BN_EVAL and pre is None
+    if frozen:
+      dt_flags = (dt_flags | _lib.MS_DT_BN_FROZEN) & ~MS_DT_BN_FOLDED        # (a folded block has no BatchNorm left to differentiate)
     rm, rv = stats if stats is not None else (None, None)
     _need16(x, x2, w, bias, gamma, beta, rm, rv)
     if not is_cb8(x) or (x2 is not None and not is_cb8(x2)):
@@ -294,9 +299,9 @@ class _ConvBlock16Fn(torch.autograd.Function):
       else:
         y = torch.empty((B, c8) + sp + (8,), dtype=x.dtype, device=x.device)
       y_raw = save = None
-      if mode == MS_BN_TRAIN:
+      if mode == MS_BN_TRAIN or frozen:
         y_raw = torch.empty((B, c8) + sp + (8,), dtype=x.dtype, device=x.device)
-        save = torch.empty((8 if (dt_flags & MS_DT_STAT_PAIR) else 4) * ctot, dtype=torch.float32, device=x.device)
+        save = torch.empty((8 if ((dt_flags & MS_DT_STAT_PAIR) and not frozen) else 4) * ctot, dtype=torch.float32, device=x.device)
       ws = workspace(d._fwd_ws, x.device)
       sync = _ensure_bn_sync(x.device) if mode == MS_BN_TRAIN else None
       folded = mode == MS_BN_EVAL and bool(dt_flags & MS_DT_BN_FOLDED)
@@ -308,7 +313,7 @@ class _ConvBlock16Fn(torch.autograd.Function):
                                        _ptr(rm), _ptr(rv), _ptr(y_raw), _ptr(y), _ptr(save), _ptr(ws), ws.numel(),
                                        _stream(), ctypes.byref(opt)), 'ms_conv_block_fwd_ex')
     ctx.geom_desc = d
-    ctx.mode, ctx.in_mode = mode, in_mode
+    ctx.mode, ctx.in_mode, ctx.frozen = mode, in_mode, frozen
     # `link`: (ops.ResidualLink, role) -- the rules of the fp32 twin (ops._ConvBlockFn)
     ctx.link = None
     if link is not None and pre is None and not ops.bn_sync_active():
@@ -331,10 +336,10 @@ class _ConvBlock16Fn(torch.autograd.Function):
   def backward(ctx, dy):
     x, x2, w, gamma, y_raw, y, save = ctx.saved_tensors
     d, mode, in_mode = ctx.geom_desc, ctx.mode, ctx.in_mode
-    if mode == MS_BN_EVAL:
+    if mode == MS_BN_EVAL and not ctx.frozen:
       raise RuntimeError('backward through an eval-mode (running-stats) ConvNormRelu is not on the path')
     need_x, need_x2, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-    need_bn = mode == MS_BN_TRAIN and ctx.needs_input_grad[4]
+    need_bn = (mode == MS_BN_TRAIN or ctx.frozen) and ctx.needs_input_grad[4]
     dy = dy.contiguous()
     dev = dy.device
     out_f32 = bool(d.dtype & MS_DT_OUT_F32)
@@ -391,12 +396,14 @@ class _ConvBlock16Fn(torch.autograd.Function):
       D['jobs'].append((part, dw, nsplit))
       ops._queue_deferred_flush()
     return (dx, dx2, None if direct_w else dw, None if direct_b else dbias, None if direct_g else dgamma,
-            None if direct_be else dbeta, None, None, None, None, None, None, None)
+            None if direct_be else dbeta, None, None, None, None, None, None, None, None)
 
 
 def conv_block16(x, w, bias, geom, mode, gamma=None, beta=None, running_mean=None, running_var=None, x2=None,
-                 in_mode=MS_IN_PLAIN, out_f32=False, bn_folded=False, link=None):
-  """One conv block in the 16-bit mode: x (and x2) cb8, result cb8 -- or plain fp32 (B, C, ...) with out_f32."""
+                 in_mode=MS_IN_PLAIN, out_f32=False, bn_folded=False, link=None, frozen=False):
+  """One conv block in the 16-bit mode: x (and x2) cb8, result cb8 -- or plain fp32 (B, C, ...) with out_f32.
+  frozen: an MS_BN_EVAL block that may be differentiated (ops.conv_block); without a gradient to compute it is the eval form."""
+  frozen = bool(frozen) and mode == MS_BN_EVAL and ops.needs_grad(x, x2, w, bias, gamma, beta)
   stats = (running_mean, running_var) if running_mean is not None else None
   flags = MS_DT[x.dtype] | (MS_DT_OUT_F32 if out_f32 else 0) | (MS_DT_BN_FOLDED if (bn_folded and mode == MS_BN_EVAL) else 0)
   if ops.stat_pair_active():
@@ -404,7 +411,7 @@ def conv_block16(x, w, bias, geom, mode, gamma=None, beta=None, running_mean=Non
   # (the links of the 16-bit modes are on only with ops.enable_residual_links16(True) / MS_LINK16=1;
   # ops.enable_chain_fusion(False) / MS_CHAIN_BN=0 switches them off together with the fp32 ones)
   link = link if (link is not None and ops.residual_links16_active() and torch.is_grad_enabled()) else None
-  return _ConvBlock16Fn.apply(x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, flags, None, link)
+  return _ConvBlock16Fn.apply(x, x2, w, bias, gamma, beta, geom, mode, in_mode, stats, flags, None, link, frozen)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -434,8 +441,10 @@ def decoder_chain16(x, blocks, logits, score, P):
     return None
   if tuple(score.shape) != (B, M, T) or score.dtype != torch.float32:
     return None
-  training = all(m.training and m.norm.track_running_stats for m in blocks)
-  if not training and any(m.training for m in blocks):
+  # (a frozen block -- layers.freeze_batchnorm -- normalises with its running statistics whatever its training flag says)
+  batch_stats = [m.training and not getattr(m, '_bn_frozen', False) for m in blocks]
+  training = all(b and m.norm.track_running_stats for b, m in zip(batch_stats, blocks))
+  if not training and any(batch_stats):
     return None
   mode = MS_BN_TRAIN if training else MS_BN_EVAL
   params = [t for m in blocks for t in (m.conv.weight, m.conv.bias, m.norm.weight, m.norm.bias)] + [logits.weight, logits.bias]

@@ -43,19 +43,21 @@ class Speech2Gesture_D(nn.Module):
   def pair_supported(self, x):
     """Can forward_pair run on x (2B, pose_feats, time) -- every block's kernels implement MS_DT_STAT_PAIR (ms_stat_pair_ok) for this
     batch, train-mode BatchNorm with local statistics, the in-launch meetings available?  Cached per input shape and tuning epoch."""
-    from ._lib import MS_BARE, MS_BN_TRAIN, MS_DT_OUT_F32, MS_LRELU
+    from ._lib import MS_BARE, MS_BN_EVAL, MS_BN_TRAIN, MS_DT_OUT_F32, MS_LRELU
     if not self.training or ops.bn_sync_active() or not ops16.in_launch_meetings():
       return False
     # a caller that hooked a block expects the reference's two calls per D-step, each on a batch of B
     if any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, '_backward_pre_hooks', None) for m in self.modules()):
       return False
     dt = getattr(self, '_ms_dt', 0)
-    key = (tuple(x.shape), dt, ops.lib().ms_tuning_epoch())
+    # (a frozen block -- layers.freeze_batchnorm -- has no statistics groups: a plain batch of 2B in any kernel)
+    bn_mode = lambda m: MS_BN_EVAL if getattr(m, '_bn_frozen', False) else MS_BN_TRAIN
+    key = (tuple(x.shape), dt, ops.lib().ms_tuning_epoch(), tuple(bn_mode(m) for m in list(self.conv2) + [self.conv3]))
     cache = self.__dict__.setdefault('_pair_ok', {})
     if key not in cache:
       ok, W = x.shape[0] % 2 == 0 and x.dim() == 3, x.shape[-1]
-      blocks = [(self.conv1[0], MS_LRELU, None)] + [(m.conv, MS_BN_TRAIN, m) for m in self.conv2] + \
-               [(self.conv3.conv, MS_BN_TRAIN, self.conv3), (self.logits, MS_BARE, None)]
+      blocks = [(self.conv1[0], MS_LRELU, None)] + [(m.conv, bn_mode(m), m) for m in self.conv2] + \
+               [(self.conv3.conv, bn_mode(self.conv3), self.conv3), (self.logits, MS_BARE, None)]
       for conv, mode, mod in blocks:
         if not ok:
           break

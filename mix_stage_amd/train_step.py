@@ -375,12 +375,22 @@ class MixStageTrainStep:
   BatchNorm buffers -- running statistics, moving averages already -- are not averaged.  The decay is a by-value kernel argument:
   it is constant, and frozen into the captured steps.  ema_state_dict() reads the average, ema_weights() runs the model on it,
   checkpoint.save_weights(..., ema=True) writes it; optimizer_state() carries it with the moments and the step clocks.
-  checkpoint.load_weights leaves the average alone: call optim_G.ema_reset() behind it to restart the average from those weights."""
+  checkpoint.load_weights leaves the average alone: call optim_G.ema_reset() behind it to restart the average from those weights.
+
+  freeze_bn (fine-tuning; every arithmetic mode): None, True (every block), 'G' / 'D', or an iterable of modules of the model and dotted
+  names ('G.unet').  The ConvNormRelu blocks under them are flagged at construction (layers.freeze_batchnorm): they normalise with
+  their running statistics whatever `training` says -- _ensure_train_mode is not involved --, never move them, and are
+  differentiated.  The flags may change between steps (layers.freeze_batchnorm, or `_bn_frozen` set by hand): the set
+  of frozen blocks is part of the captured-graph key, a step under new flags is captured anew.  Composes with lr_schedule, ema_decay and on_bad_step."""
 
   def __init__(self, model, lr=1e-4, clip=1.0, use_graphs=True, process_group=None, time_steps=64, overlap_wgrad=False,
                bn_sync='local', overlap_allreduce=False, grad_buckets=None, grad_exchange='fp32', loss_scale=None, lr_schedule=None,
-               ema_decay=None):
+               ema_decay=None, freeze_bn=None):
     self.model = model
+    # frozen BatchNorm statistics (fine-tuning): flags on the blocks, applied here; layers.freeze_batchnorm changes them later
+    for root in layers.freeze_bn_roots(model, freeze_bn):
+      layers.freeze_batchnorm(root)
+    self._bn_blocks = None
     self.ema_decay = ops.check_ema_decay(ema_decay, 'MixStageTrainStep(ema_decay=)') if ema_decay is not None else None
     self._in_ema_weights = False
     # one scheduler per optimizer, as in the reference (TR:311-313): each is chained on its own network's learning rate
@@ -665,7 +675,7 @@ class MixStageTrainStep:
     for mod in mods:
       if not mod.training:
         self.model.train()
-        self._mods = None           # (re-list next time: whoever switched modes may also have edited the tree)
+        self._mods = self._bn_blocks = None           # (re-list next time: whoever switched modes may also have edited the tree)
         return
 
   # ---- public ----------------------------------------------------------------------------------------------
@@ -797,9 +807,14 @@ class MixStageTrainStep:
 
   def _graph_step(self, k, pose_branch, audio, labels, pose, style, inputs_unchanged=False):
     self.model._lambda_host_writes = False   # the captured loss kernels read the device tensor written below
-    key = (k, pose_branch, tuple(audio.shape), tuple(pose.shape))
-    if self._static is None or self._static['key_shapes'] != key[2:]:
-      self._static = dict(key_shapes=key[2:], audio=audio.clone(), labels=labels.clone(), pose=pose.clone(),
+    # (the set of frozen-BatchNorm blocks is part of the key: a captured step holds the launches of the flags it was captured with.
+    # The flags are plain attributes anybody may set: they are read every step, ~50 dictionary look-ups)
+    blocks = self._bn_blocks
+    if blocks is None:
+      blocks = self._bn_blocks = [b for b in self.model.modules() if isinstance(b, layers.ConvNormRelu)]
+    key = (k, pose_branch, tuple(audio.shape), tuple(pose.shape), tuple([b.__dict__.get('_bn_frozen', False) for b in blocks]))
+    if self._static is None or self._static['key_shapes'] != key[2:4]:
+      self._static = dict(key_shapes=key[2:4], audio=audio.clone(), labels=labels.clone(), pose=pose.clone(),
                           style=style.clone())
       self._graphs = {}
     st = self._static
