@@ -6,21 +6,16 @@ namespace ms {
 
 namespace {
 
-Conv16Plan fwd_plan16(const ms_conv_desc* d) {
-  const BlockGeo g = geo_of(d);
-  return plan_conv16(g.nd, d->Cout, d->groups, d->Cin, d->KH, d->KW, d->SH, d->SW, d->B, d->OH, d->OW, 1, g.up2 != 0);
-}
+// (the arithmetic: conv16_plan.h, where tests/helpers/conv16_plan_host.cpp reads it too)
+Conv16Plan fwd_plan16(const ms_conv_desc* d) { return fwd_plan16_of(d); }
 struct Dgrad16 : DgradGeo { Conv16Plan pl; };
 Dgrad16 dgrad_plan16(const ms_conv_desc* d) {
   Dgrad16 r;
   static_cast<DgradGeo&>(r) = dgrad_geo_of(d);
-  r.pl = plan_conv16(geo_of(d).nd, d->Cin, r.tg, r.tcog, r.jh, r.jw, 1, 1, d->B, cdiv(d->H, d->SH), cdiv(d->W, d->SW), r.ncls, false);
+  r.pl = dgrad_plan16_of(d, r);
   return r;
 }
-Wgrad16Plan wgrad_plan16(const ms_conv_desc* d) {
-  const BlockGeo g = geo_of(d);
-  return plan_wgrad16(g.nd, d->Cout, d->Cin, d->groups, d->KH, d->KW, d->SH, d->SW, d->B, d->OH, d->OW, g.up2 != 0);
-}
+Wgrad16Plan wgrad_plan16(const ms_conv_desc* d) { return wgrad_plan16_of(d); }
 size_t fwd_a_bytes(const ms_conv_desc* d, const Conv16Plan& pl) {
   return conv16_weight_bytes(pl, d->Cout, d->groups, d->Cin, d->KH, d->KW, 1);
 }

@@ -11,28 +11,17 @@ struct BlockGeo { int dt, nd, one_d, up2, bcast, C, C8, cin_tot, cin8_tot, npix,
 inline BlockGeo geo_of(const ms_conv_desc* d) {
   BlockGeo g;
   g.dt = dt_of(d);
-  g.one_d = d->H == 1 && d->KH == 1;
-  g.nd = g.one_d ? 1 : 2;
+  g.nd = plan_nd_of(d);
+  g.one_d = g.nd == 1;
   g.C = d->groups * d->Cout; g.C8 = c8_of(g.C);
-  g.bcast = d->in_mode == MS_IN_BCAST; g.up2 = d->in_mode == MS_IN_UP2ADD;
+  g.bcast = d->in_mode == MS_IN_BCAST; g.up2 = plan_up2_of(d);
   g.cin_tot = g.bcast ? d->Cin : d->groups * d->Cin; g.cin8_tot = c8_of(g.cin_tot);
   g.npix = d->B * d->OH * d->OW; g.hw = d->OH * d->OW; g.khw = d->KH * d->KW;
   return g;
 }
 inline size_t wsize_of(const ms_conv_desc* d) { return (size_t)d->groups * d->Cout * d->Cin * d->KH * d->KW; }
 
-// The data gradient as SH*SW dense stride-1 convs of dy_raw, one per output-parity class: groups and reduction channels per group
-// (a broadcast input sums all groups into the same channels), taps per class.
-struct DgradGeo { int tg, tcog, jh, jw, ncls; };
-inline DgradGeo dgrad_geo_of(const ms_conv_desc* d) {
-  const bool bcast = d->in_mode == MS_IN_BCAST;
-  DgradGeo r;
-  r.tg = bcast ? 1 : d->groups;
-  r.tcog = bcast ? d->groups * d->Cout : d->Cout;
-  r.jh = cdiv(d->KH, d->SH); r.jw = cdiv(d->KW, d->SW);
-  r.ncls = d->SH * d->SW;
-  return r;
-}
+// (DgradGeo, dgrad_geo_of: conv16_plan.h)
 
 // Per class: padding, output extent and scatter phase (class 0 has the largest extent: its values are the launch's own); the output
 // scatter strides.  Returns the flops of all classes.  PatchArgs and Conv16Args share these field names.

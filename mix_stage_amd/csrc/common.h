@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include "conv16_plan.h"
 #include "mixstage.h"
 #include "mixstage_aux.h"
 
@@ -43,7 +44,7 @@ inline void done_on_device(unsigned long long& mask) {
 }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// (cdiv: conv16_plan.h, which also builds without HIP)
 __host__ __device__ inline int cdiv_dev(int a, int b) { return (a + b - 1) / b; }
 
 // Cross-lane sums on the VALU (DPP row rotations inside a 16-lane row, v_permlane16_swap / v_permlane32_swap across rows):

@@ -6,6 +6,7 @@
 // v_mfma_f32_32x32x16_{bf16,f16} (8 consecutive k = 8 consecutive channels at one tap), so the matrix operands go
 // HBM -> LDS -> VGPR as 16-byte moves with no transposition: every tap or stride offset is a whole number of vectors.
 #pragma once
+#include "conv16_plan.h"
 #include "kernels.h"
 
 namespace ms {
@@ -18,7 +19,6 @@ inline int sg_of(const ms_conv_desc* d) { return (d->dtype & MS_DT_STAT_PAIR) ? 
 // 16-bit BN_TRAIN blocks with MS_DT_STAT_PAIR (api16.hip)
 bool stat_pair16_ok(const ms_conv_desc* d);
 inline bool bn_folded_of(const ms_conv_desc* d) { return d->mode == MS_BN_EVAL && (d->dtype & MS_DT_BN_FOLDED) != 0; }
-inline int c8_of(int c) { return (c + 7) >> 3; }
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
@@ -61,11 +61,7 @@ struct Conv16Args {
   int is_dgrad;
 };
 
-struct Conv16Plan {
-  int ok, wm, wn, nwn, tw, th, tiles_y, tiles_x, n_tiles, ck8, nchunks, pc, lds_bytes, dma, nstg;
-};
-Conv16Plan plan_conv16(int nd, int Mg, int groups, int Kc, int KH, int KW, int SH, int SW, int B, int OH, int OW, int zmul,
-                       bool up2);
+// (Conv16Plan, plan_conv16: conv16_plan.h)
 // bytes of the prepared A operand for (rows per group Mg, groups, input channels Kc, taps) under plan pl, ncls classes
 size_t conv16_weight_bytes(const Conv16Plan& pl, int Mg, int groups, int Kc, int KH, int KW, int ncls);
 int launch_conv16(int dt, const Conv16Args& a, const Conv16Plan& pl, int KW, bool up2, double flops, double bytes,
@@ -123,8 +119,7 @@ struct Wgrad16Args {
   int accumulate;       // splits == 1 only: out += result instead of out = result (queued launches)
   size_t out_split_stride;
 };
-struct Wgrad16Plan { int tp, tw, th, tiles_y, tiles_x, n_tiles, splits, tiles_per_split, ktg, pcx, lds_bytes, nstg, npx; };
-Wgrad16Plan plan_wgrad16(int nd, int Cog, int Cig, int groups, int KH, int KW, int SH, int SW, int B, int OH, int OW, bool up2);
+// (Wgrad16Plan, plan_wgrad16: conv16_plan.h)
 int launch_wgrad16(int dt, const Wgrad16Args& a, const Wgrad16Plan& pl, bool up2, double flops, double bytes, hipStream_t s);
 // the same launch queued (process-wide queue) for wgrad16_flush: many blocks' kernels side by side in one multi-block launch
 constexpr int WG16_MAX_JOBS = 20;    // 20 x sizeof(Wgrad16Args) + the table of block ranges stays below the 4 KB of kernel arguments

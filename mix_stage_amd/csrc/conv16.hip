@@ -9,12 +9,7 @@
 namespace ms {
 
 // ---------------------------------------------------------------------------------------------
-// planning
-static int pow2_at_least(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
+// planning (plan_conv16 itself is host-only code in conv16_plan.h)
 static int ilog2(int v) {
   int l = 0;
   while ((1 << l) < v) ++l;
@@ -22,83 +17,13 @@ static int ilog2(int v) {
 }
 
 int g_conv16_force_wm = 0, g_conv16_force_wn = 0;     // tuning knob (ms_debug_set_conv16_tile)
-int g_conv16_dma = 1;                                 // tuning knob: 0 = register-staged path everywhere
+int g_conv16_dma = CONV16_DMA_DEFAULT;                // tuning knob: 0 = register-staged path everywhere
 int g_conv16_wide8 = 0;                               // tuning knob: 8-wave form of the 128 x 128 tile (measured: no gain)
 int g_conv16_dbg = 0;
 int g_conv16_ring = 0;                                // tuning knob: force the LDS-DMA ring depth (0 = planner)
-int g_conv16_big_stages = 2;                          // tuning knob: 0 = short stages everywhere (ms_debug_set_conv16_ring, bit 8 of the flags)
+int g_conv16_big_stages = CONV16_BIG_STAGES_DEFAULT;  // tuning knob: 0 = short stages everywhere (ms_debug_set_conv16_ring, bit 8 of the flags)
 
-Conv16Plan plan_conv16(int nd, int Mg, int groups, int Kc, int KH, int KW, int SH, int SW, int B, int OH, int OW, int zmul,
-                       bool up2) {
-  Conv16Plan pl = {};
-  if (!(KW == 1 || KW == 2 || KW == 3 || KW == 4 || KW == 8)) return pl;
-  if (nd == 2 && SH != SW) return pl;
-  if (up2 && !(KW == 3 && SW == 1 && nd == 1)) return pl;
-  const int rows = nd == 1 ? B : OH, imgs = nd == 1 ? 1 : B;
-  const int S = SW, SV = nd == 1 ? 1 : SH;
-  const int ck8 = conv16_ck8(KW);
-  // candidate tiles, largest first: the first one that fills the chip (>= 192 workgroups), else the smallest
-  const int cand[3][2] = {{2, 2}, {1, 2}, {1, 1}};
-  for (int c = 0; c < 3; ++c) {
-    int wm = cand[c][0], wn = cand[c][1], nwn = 2;
-    const int bm = 64 * wm, bn = 64 * wn;
-    // the 128 x 128 tile runs as 8 waves (2 x 4, 64 x 32 each) on the LDS-DMA path: same tile, half the per-wave overhead
-    if (c == 0 && g_conv16_wide8 && g_conv16_dma && !up2) { wn = 1; nwn = 4; }
-    const int nt = 128 * nwn;
-    if (g_conv16_force_wm && (cand[c][0] != g_conv16_force_wm || cand[c][1] != g_conv16_force_wn)) continue;
-    if (c == 0 && Mg < 128) continue;          // 128-row tiles only for layers with >= 128 rows per group
-    const int tw = std::min(pow2_at_least(OW), bn), th = bn / tw;
-    const int pc = (tw - 1) * S + KW;
-    const int tiles_y = cdiv(rows, th), tiles_x = cdiv(OW, tw);
-    const long nwg = (long)imgs * tiles_y * tiles_x * cdiv(Mg, bm) * groups * zmul;
-    const bool fits = ck8 * th * pc <= CONV16_NP * nt;
-    if (!fits) continue;
-    // the 128 x 128 tile only when it leaves >= 384 workgroups: with 256 (the grouped decoder) every CU would hold ONE
-    // workgroup whose LDS reads and MFMAs alternate; 64 x 128 tiles put two on a CU and they overlap (20.2 -> 18.7 us)
-    if (nwg >= (c == 0 ? 384 : 192) || c == 2 || g_conv16_force_wm) {
-      pl.ok = 1; pl.wm = wm; pl.wn = wn; pl.nwn = nwn; pl.tw = tw; pl.th = th; pl.tiles_y = tiles_y; pl.tiles_x = tiles_x;
-      pl.n_tiles = imgs * tiles_y * tiles_x;
-      pl.ck8 = ck8; pl.nchunks = cdiv(c8_of(Kc), ck8); pl.pc = pc;
-      pl.lds_bytes = 2 * (KW * ck8 * bm + ck8 * th * pc + 1) * 16;
-      // 64 x 64 (and 64 x 128) tiles on at most 256 workgroups (one per CU, the small layers): stages of twice the channels.  Measured per
-      // launch: 256->256 k3 T=64 12.9 -> 9.9 us, k4 s2 13.9 -> 10.8, 3x3 (8,16) 23.0 -> 16.8, 3x8 38.0 -> 30.2; the tiles that share
-      // a CU (decoder, first audio-encoder layers) lose 10 % with it and keep the short stages
-      if (g_conv16_dma && !up2 && (c == 2 || c == 1) && nwg <= 256 && g_conv16_big_stages && 2 * ck8 * th * pc <= CONV16_NP * nt &&
-          2 * (KW * 2 * ck8 * bm + cdiv(2 * ck8 * th * pc, nt) * nt) * 16 <= 160 * 1024) {
-        int mult = 2;
-        // four times the channels where two such stages still fit (k <= 3 taps per row) and the reduction has more than 2 of them
-        if (g_conv16_big_stages >= 2 && c == 2 && KW <= 3 && 4 * ck8 * th * pc <= CONV16_NP * nt && c8_of(Kc) > 2 * ck8 &&
-            2 * (KW * 4 * ck8 * bm + cdiv(4 * ck8 * th * pc, nt) * nt) * 16 <= 160 * 1024)
-          mult = 4;
-        const int ck8b = mult * ck8;
-        pl.ck8 = ck8b; pl.nchunks = cdiv(c8_of(Kc), ck8b);
-        const int stage = (KW * ck8b * bm + cdiv(ck8b * th * pc, nt) * nt) * 16;
-        const int nstages = pl.nchunks * KH;
-        int nstg = std::min(std::min(CONV16_MAX_RING, nstages + 1), 160 * 1024 / stage);
-        if (g_conv16_ring >= 2) nstg = std::min(nstg, g_conv16_ring);
-        pl.dma = 1; pl.nstg = std::max(2, nstg); pl.lds_bytes = pl.nstg * stage;
-        return pl;
-      }
-      if (g_conv16_dma && !up2) {
-        // LDS-DMA ring: up to 4 buffers; when the grid holds more workgroups than CUs the ring is kept below half of the
-        // CU's LDS so that two workgroups share a CU (one computes while the other waits for its stage)
-        const int stage = (KW * ck8 * bm + cdiv(ck8 * th * pc, nt) * nt) * 16;
-        const int budget = nwg > 256 ? 80 * 1024 : 160 * 1024;
-        // (depth up to 8: the small layers -- 64 x 64 tiles, a handful of workgroups -- are pure latency chains, and with the
-        // whole reduction in flight at once they pay one memory round trip instead of one per 3 stages)
-        const int nstages = cdiv(c8_of(Kc), ck8) * KH;
-        int nstg = std::min(std::min(CONV16_MAX_RING, nstages + 1), budget / stage);
-        if (nstg < 2) nstg = std::min(4, 160 * 1024 / stage);
-        if (g_conv16_ring >= 2) nstg = std::min(nstg, g_conv16_ring);   // knob: cap the depth
-        if (nstg >= 2) { pl.dma = 1; pl.nstg = nstg; pl.lds_bytes = nstg * stage; }
-      }
-      (void)SV;
-      return pl;
-    }
-  }
-  return pl;
-}
-
+// (plan_conv16: conv16_plan.h)
 size_t conv16_weight_bytes(const Conv16Plan& pl, int Mg, int groups, int Kc, int KH, int KW, int ncls) {
   (void)Kc;
   const int bm = 64 * pl.wm;

@@ -64,9 +64,7 @@ __device__ inline u32x4 buf_load_v(__amdgpu_buffer_rsrc_t r, unsigned voff, unsi
   return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
 }
 
-constexpr int conv16_ck8(int KW) { return KW == 8 ? 2 : 4; }
-constexpr int CONV16_NP = 6;      // patch vectors a thread stages per stage at most (plan_conv16 keeps CK8*TH*PC <= 6*256)
-constexpr int CONV16_MAX_RING = 8; // LDS-DMA ring depth limit (buffers; one less is in flight)
+// (conv16_ck8, CONV16_NP, CONV16_MAX_RING: conv16_plan.h)
 
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n (the instruction takes an immediate)
 __device__ inline void wait_vmcnt(int n) {
@@ -810,7 +808,7 @@ __global__ __launch_bounds__(128 * NWN) void conv16_kernel(const Conv16Args p) {
     };
     switch (wcount) {
 #define MS_KLOOP(N) case N: k_loop(std::integral_constant<int, N>{}); break;
-      MS_KLOOP(0) MS_KLOOP(6) MS_KLOOP(8) MS_KLOOP(10) MS_KLOOP(11) MS_KLOOP(13) MS_KLOOP(18) MS_KLOOP(20) MS_KLOOP(24)
+      CONV16_WAIT_LITERALS(MS_KLOOP)
 #undef MS_KLOOP
       default: k_loop(std::integral_constant<int, -1>{}); break;
     }

@@ -25,18 +25,10 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 // workgroups a layer's launch aims for through pixel splits (ms_debug_set_wgrad16_target).  The trainer launches the layers'
 // kernels side by side (ms_wgrad_flush), so a layer need not fill the chip alone; measured on the train step: 512 -> 3.17 ms,
 // 256 -> 3.12, 128 -> 3.06, 64 -> 3.15 per G-step (fewer, longer workgroups leave fewer partial slabs to store and reduce)
-int g_wgrad16_target_wgs = 128;
+int g_wgrad16_target_wgs = WGRAD16_TARGET_WGS_DEFAULT;
 extern int g_conv16_dbg;
 
-// LDS pitches (16-byte vectors) of a channel block's pixels.  The transposed reads of one MFMA operand touch FOUR channel blocks
-// at once (lanes 0-31 of ds_read_b64_tr_b16: 4 rows x 16 banks each), so the block pitch must be = 16 banks (4 vectors) mod 64
-// banks: the natural pitches -- 64 vectors for dy, TH*PCX = 66 for a k3 row -- put the four blocks on the same / overlapping
-// banks (SQ_LDS_BANK_CONFLICT was 40 % of SQ_LDS_IDX_ACTIVE on the decoder layer).
-constexpr int WG16_DP = 68;   // dy: 64 pixels + 4
-__host__ __device__ inline int wg16_xpitch(int thpcx) { return ((thpcx + 11) & ~15) + 4; }   // smallest pitch >= thpcx that is 4 mod 16
-constexpr int WG16_DYV = 8 * WG16_DP;    // vectors of the dy part of a stage
-constexpr int WG16_NPX = 5;   // register-staged form (upsample-add input): input-row vectors a thread stages per tile at most
-
+// (LDS pitches WG16_DP / wg16_xpitch / WG16_DYV / WG16_NPX: conv16_plan.h, beside plan_wgrad16)
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 // one transposed 4-row read at a byte address (constant byte offsets fold into the instruction's offset field)
 __device__ __forceinline__ unsigned long long tr_read_b64(const char* ptr) {
@@ -355,7 +347,7 @@ __global__ __launch_bounds__(256) void wgrad16_multi_kernel(const Wgrad16Batch b
 // pixel per step, loads its dy vector and the KH*KW input values around it (channel 0 of the cb8 input: neighbouring lanes
 // read neighbouring pixels, served by L1 / L2) and keeps 8 x KH*KW running sums.  Fixed-order reduction: lanes (DPP), the 4
 // waves through LDS, the splits by the caller's slab reduction like every other weight gradient.
-constexpr int WGC1_MAX_TAPS = 9;
+// (WGC1_MAX_TAPS: conv16_plan.h)
 
 template <typename DT>
 __global__ __launch_bounds__(256) void wgrad16_c1_kernel(const Wgrad16Args p) {
@@ -543,62 +535,19 @@ __global__ __launch_bounds__(256) void wgrad16_c1_3x3_kernel(const Wgrad16Args p
 }
 
 bool wgrad16_c1_ok(const Wgrad16Args& a, bool up2) {
-  return !up2 && a.Cig == 1 && a.groups == 1 && a.KH * a.KW <= WGC1_MAX_TAPS;
+  return wgrad16_c1_shape(a.Cig, a.groups, a.KH, a.KW, up2);
 }
 
 // ---------------------------------------------------------------------------------------------
-static int pow2_at_least(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
 static int ilog2(int v) {
   int l = 0;
   while ((1 << l) < v) ++l;
   return l;
 }
 
-int g_wgrad16_ring = 2;        // LDS-DMA ring depth (ms_debug_set_wgrad16_ring)
+int g_wgrad16_ring = WGRAD16_RING_DEFAULT;        // LDS-DMA ring depth (ms_debug_set_wgrad16_ring)
 
-Wgrad16Plan plan_wgrad16(int nd, int Cog, int Cig, int groups, int KH, int KW, int SH, int SW, int B, int OH, int OW, bool up2) {
-  Wgrad16Plan pl = {};
-  const int rows = nd == 1 ? B : OH, imgs = nd == 1 ? 1 : B;
-  pl.tp = KW == 1 ? 1 : KW == 3 ? 3 : (KW % 4 == 0) ? 4 : (KW == 2 ? 2 : 0);
-  if (!pl.tp) return pl;
-  pl.ktg = KW / pl.tp;
-  pl.tw = std::min(pow2_at_least(OW), 64);
-  pl.th = 64 / pl.tw;
-  pl.pcx = (pl.tw - 1) * SW + pl.tp;
-  const int xp = wg16_xpitch(pl.th * pl.pcx), xv = 8 * xp;
-  pl.npx = cdiv(xv, 256);                              // 256-vector slabs of input rows per tile
-  if (up2 && pl.npx > WG16_NPX) return (pl.tp = 0, pl);
-  if (xv > 65535) return (pl.tp = 0, pl);
-  pl.tiles_y = cdiv(rows, pl.th); pl.tiles_x = cdiv(OW, pl.tw);
-  pl.n_tiles = imgs * pl.tiles_y * pl.tiles_x;
-  // pixel splits: fill ~2 workgroups per CU, at least 2 tiles per workgroup
-  const long base = (long)cdiv(Cog, 64) * cdiv(Cig, 64) * groups * KH * pl.ktg;
-  int splits = (int)std::max<long>(1, std::min<long>((g_wgrad16_target_wgs + base - 1) / base, pl.n_tiles / 2));
-  splits = std::min(splits, 64);
-  pl.tiles_per_split = cdiv(pl.n_tiles, std::max(1, splits));
-  pl.splits = cdiv(pl.n_tiles, pl.tiles_per_split);
-  if (Cig == 1 && groups == 1 && KH == 3 && KW == 3 && SW == 1 && !up2) {
-    // single-input-channel 3x3 block (wgrad16_c1_3x3_kernel: a 33 MB stream over dy at the headline size): slabs = row splits x
-    // 64-column tiles, one 4-wave workgroup each -- enough of them (256) to keep the stream in flight; a slab is Cog x 9 floats
-    const int col_tiles = cdiv(OW, 64), total_rows = imgs * rows;
-    const int row_splits = std::max(1, std::min(256 / col_tiles, total_rows / 8));
-    const int rps = cdiv(total_rows, row_splits);
-    pl.splits = cdiv(total_rows, rps) * col_tiles;
-    pl.tiles_per_split = cdiv(pl.n_tiles, pl.splits);            // (the MFMA kernel is not used for this block)
-  }
-  // register-staged form (upsample-add input): two buffers.  LDS-DMA form: a ring of g_wgrad16_ring buffers of whole 64-vector
-  // wave slabs (17 KB for a k3 row: two buffers leave room for four workgroups per CU)
-  const int stage = (WG16_DYV + cdiv(xv, 64) * 64) * 16;
-  pl.nstg = up2 ? 2 : std::max(2, std::min(std::min(g_wgrad16_ring, pl.tiles_per_split + 1), 160 * 1024 / stage));
-  pl.lds_bytes = up2 ? 2 * (WG16_DYV + xv + 1) * 16 : pl.nstg * stage;
-  if (pl.lds_bytes > 160 * 1024) return (pl.tp = 0, pl);
-  (void)SH;
-  return pl;
-}
+// (plan_wgrad16: conv16_plan.h)
 
 template <typename DT, int TP, bool UP2, int NPXT>
 static int launch_w(const Wgrad16Args& a, int lds, int nwg, hipStream_t s) {
@@ -626,12 +575,7 @@ static int launch_wm(const Wgrad16Batch& b, int lds, hipStream_t s) {
   return 0;
 }
 
-// npxt: slots of input rows a thread keeps in registers (3, 5) or 0 = the per-tile loop (layers with a few pixels per row).
-// Queued jobs (wgrad16_flush) all take the 5-slot instance up to 5 slots: a slot beyond a job's rows is a wave-uniform skip, and
-// the jobs of a backward pass then share ONE launch per number of taps -- with 3- and 5-slot instances apart, a single
-// 192-workgroup job ran alone on a corner of the chip for 55 us.  (A universal kernel holding every instance behind a switch was
-// tried: the register allocator gives the cases disjoint accumulator ranges -- 168 VGPR + 128 AGPR, 3.7 KB of scratch.)
-inline int wg16_npxt(int npx) { return npx <= 3 ? 3 : npx <= 5 ? 5 : 0; }
+// (wg16_npxt: conv16_plan.h)  Queued jobs take the 5-slot instance up to 5 slots.
 inline int wg16_npxt_queued(int npx) { return npx <= 5 ? 5 : 0; }
 
 template <typename DT, int TP>

@@ -5,6 +5,7 @@ import torch
 
 from helpers import round16_model as M
 from helpers.fp16_block_table import TABLE, SCALED, BY_ID, TINY_DY, LOSS_SCALES, OVERFLOW
+from helpers.conv16_plan_table import ENTRIES as PLAN_ENTRIES
 
 TYPES = [torch.bfloat16, torch.float16]
 FLIP_FRAC = 2e-3                # _case's flip_frac
@@ -73,6 +74,13 @@ def test_case_separates_the_types_and_stays_off_the_kink(c):
   assert f['kink share'] <= FLIP_FRAC / 2 and b['kink share'] >= f['kink share'], (f['kink share'], b['kink share'])
   # the model's fp16 figures are of the size of one fp16 rounding (u = 2^-11), never of bf16's
   assert all(2.0 ** -14 <= f[k] <= 2.0 ** -10 for k in checks), {k: f[k] for k in checks}
+
+
+@pytest.mark.parametrize('c', PLAN_ENTRIES, ids=[c['id'] for c in PLAN_ENTRIES])
+def test_plan_table_case_separates_the_types_and_stays_off_the_kink(c):
+  """The plan-class shapes of tests/helpers/conv16_plan_table.py (tests/test_gpu_conv16_plans.py runs them in fp16 under
+  bars='dtype'), held to the same conditions with the seeds that test uses."""
+  test_case_separates_the_types_and_stays_off_the_kink(c)
 
 
 @pytest.mark.parametrize('cid', SCALED)

@@ -37,9 +37,11 @@ def test_mirror_constants_are_the_sources():
   assert _int('wgrad_patch.hip', r'pl\.n_tiles < \(g_patch_min_wgs > 0 \? (\d+) : 1\)') == T.PATCH_MIN_TILES
   assert _int('conv_patch.hip', r'\nint g_patch_min_wgs = (\d+);') > 0
   assert _int('conv_igemm.hip', r'if \(tiles < (\d+)\) splits = \(int\)\(\(512 \+ tiles - 1\) / tiles\);') == T.GATHER_TILE_TARGET
-  assert _int('wgrad16.hip', r'\nint g_wgrad16_target_wgs = (\d+);') == T.WG16_TARGET_WGS
-  assert _int('wgrad16.hip', r'constexpr int WG16_NPX = (\d+);') == T.WG16_NPX
-  assert _int('wgrad16.hip', r'splits = std::min\(splits, (\d+)\);') == T.WG16_SPLITS_MAX
+  # (plan_wgrad16 and its constants live in conv16_plan.h; wgrad16.hip defines the knob from the header's default)
+  assert '\nint g_wgrad16_target_wgs = WGRAD16_TARGET_WGS_DEFAULT;' in _src('wgrad16.hip')
+  assert _int('conv16_plan.h', r'WGRAD16_TARGET_WGS_DEFAULT = (\d+);') == T.WG16_TARGET_WGS
+  assert _int('conv16_plan.h', r'constexpr int WG16_NPX = (\d+);') == T.WG16_NPX
+  assert _int('conv16_plan.h', r'splits = std::min\(splits, (\d+)\);') == T.WG16_SPLITS_MAX
   # the wave form of the slab reduction and the 512-block cap of the other two
   m = re.search(r'jb\.wave = \(jb\.splits >= (\d+) && jb\.n <= (\d+)\) \? 1 : 0;', _src('conv_igemm.hip'))
   assert m and (int(m.group(1)), int(m.group(2))) == (T.REDUCE_WAVE_SPLITS, T.REDUCE_WAVE_N)
@@ -47,8 +49,8 @@ def test_mirror_constants_are_the_sources():
   assert m and (int(m.group(1)), int(m.group(2))) == (T.REDUCE_PER_BLOCK, T.REDUCE_BLOCK_CAP)
   # the slot rule of queued 16-bit jobs, the pitch it rests on, and the wave_kind numbering
   assert 'inline int wg16_npxt_queued(int npx) { return npx <= 5 ? 5 : 0; }' in _src('wgrad16.hip')
-  assert 'inline int wg16_npxt(int npx) { return npx <= 3 ? 3 : npx <= 5 ? 5 : 0; }' in _src('wgrad16.hip')
-  assert 'inline int wg16_xpitch(int thpcx) { return ((thpcx + 11) & ~15) + 4; }' in _src('wgrad16.hip')
+  assert 'inline int wg16_npxt(int npx) { return npx <= 3 ? 3 : npx <= 5 ? 5 : 0; }' in _src('conv16_plan.h')
+  assert 'inline int wg16_xpitch(int thpcx) { return ((thpcx + 11) & ~15) + 4; }' in _src('conv16_plan.h')
   assert 'a.wave_kind = mode ? 5 + mode : 2 * S + (wave == 2 ? 1 : 0);' in _src('wgrad_patch.hip')
   cases = re.findall(r'case (\d): wgrad_wave_body<(\d), (\d), (\d)(?:, (\d))?>', _src('wgrad_patch.hip'))
   assert cases == [('2', '1', '2', '2', ''), ('3', '1', '1', '4', ''), ('4', '2', '2', '2', ''), ('5', '2', '1', '4', ''),
