@@ -97,8 +97,8 @@ int ms_abi_version(void);
 int ms_stat_pair_ok(const ms_conv_desc* d);
 
 /* Bytes of scratch the forward / backward of this block needs.
- * The workspace contract -- for these two, ms_decoder_chain_workspace, ms_decoder_chain_eval_workspace, ms_bn_bwd_workspace and
- * the `partials` / seg_scratch arguments of the loss and optimizer entry points (ms_reduce_partials_count):
+ * The workspace contract -- for these two, ms_decoder_chain_workspace, ms_decoder_chain_eval_workspace, ms_bn_bwd_workspace,
+ * ms_dropout_bn_workspace and the `partials` / seg_scratch arguments of the loss and optimizer entry points (ms_reduce_partials_count):
  *   - the contents are unspecified on entry and on return: a call writes what it reads, whatever the buffer held (NaN bit patterns
  *     included), and leaves nothing there that a later call relies on -- nothing is carried between calls through a workspace;
  *   - the bytes the size function names are the only ones touched: a buffer of exactly that size, with live tensors right behind
@@ -366,6 +366,40 @@ int ms_bn_bwd_sums(const float* dy, const float* y_raw, const float* save, float
                    void* workspace, size_t workspace_bytes, void* stream);
 int ms_bn_bwd_apply(const float* dy, const float* y_raw, const float* save, const float* gamma, const float* sums_global,
                     double n_global, float* dyr, int B, int C, int HW, float slope, void* stream);
+
+/* Dropout inside a block (layers.py:32-78 with p > 0; the order there is conv (+bias) -> dropout(p) -> BatchNorm -> (Leaky)ReLU,
+ * so the batch statistics are those of the DROPPED conv output).  A block = conv (MS_BARE block; 16-bit modes: with
+ * MS_DT_OUT_F32) + the pieces below, and its backward = ms_dropout_bn_bwd + the bare block's backward on dyr -- the composition of
+ * the cross-rank BatchNorm above.  y_raw (B, C, HW) fp32 stays UNDROPPED in memory: no mask tensor exists, every pass regenerates
+ * the mask bits of the values it reads.
+ *   the mask    Philox4x32-10, key (seed lo, seed hi), counter (e >> 2, site, step, 0); element e takes word e & 3 of that call.
+ *               e: the element's index in (B, C, HW) order -- or, channelwise (nn.Dropout2d), b * C + c: a whole plane lives or
+ *               dies.  Keep iff word >= min(floor(p * 2^32 + 0.5), 0xffffffff); kept values are multiplied by (float)(1 / (1 - p)).
+ *               The masks are not torch's: statistically equivalent, not bit-equal.
+ *   state       4 int32 device words: seed lo, seed hi, step, reserved 0 -- read when the kernel RUNS, so a captured step draws
+ *               fresh masks at every replay once ms_dropout_advance (one thread: step += 1) leads it.
+ *   site        by value: module id + (visit << 20); forward and backward of one pass hand over the same site.
+ *   p           0 <= p < 1; anything else is an error before any launch, as are a NULL state and a workspace below
+ *               ms_dropout_bn_workspace(B, C, HW) bytes (0 while B * HW <= 4096: one workgroup then owns a channel; the workspace
+ *               contract above holds).
+ *   ms_dropout_bn_fwd   x = m * y_raw -> save = mean|invstd|scale|shift of x, running statistics update, y = lrelu(x*scale+shift).
+ *                       frozen != 0: scale / shift from the running statistics, which are only read (MS_DT_BN_FROZEN's arithmetic).
+ *   ms_dropout_bn_bwd   dyr = m * gamma*invstd*(dz - mean(dz) - xhat*mean(dz*xhat)), dz = dy*lrelu'(x*scale+shift), xhat from x;
+ *                       dgamma = sum dz*xhat, dbeta = sum dz (both NULL: not written).  frozen != 0: without the two mean terms.
+ *                       Channels of at most 1024 values take their statistics again from x, in double (`eps` is the forward's):
+ *                       with a handful of values per channel dy_raw is a small difference of nearly equal terms.
+ *   ms_dropout_mask     out[i] = m of mask index i / inner, i < n (inner = 1: element dropout; HW: channel dropout) -- for tests
+ *                       and reference implementations.
+ * Every reduction runs in a fixed order: the same bits run to run, captured or eager. */
+size_t ms_dropout_bn_workspace(int B, int C, int HW);
+int ms_dropout_bn_fwd(const float* y_raw, const float* gamma, const float* beta, float* running_mean, float* running_var, float* y,
+                      float* save, int B, int C, int HW, float slope, float eps, float momentum, int frozen, int channelwise, double p,
+                      uint32_t site, const int32_t* state, void* workspace, size_t workspace_bytes, void* stream);
+int ms_dropout_bn_bwd(const float* dy, const float* y_raw, const float* save, const float* gamma, float* dyr, float* dgamma, float* dbeta,
+                      int B, int C, int HW, float slope, float eps, int frozen, int channelwise, double p, uint32_t site,
+                      const int32_t* state, void* workspace, size_t workspace_bytes, void* stream);
+int ms_dropout_advance(int32_t* state, void* stream);
+int ms_dropout_mask(float* out, size_t n, int inner, double p, uint32_t site, const int32_t* state, void* stream);
 
 /* AudioEncoder resize (layers.py:197): bilinear to (T,1), align_corners=False, == 1-D lerp in time
  * of frequency column F/2.   x (B,C,Tin,F) -> y (B,C,Tout). */

@@ -111,6 +111,14 @@ SIGNATURES = {
     'ms_bn_bwd_workspace': (c_size_t, [c_int, c_int]),
     'ms_bn_bwd_sums': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, _P, c_size_t, _P]),
     'ms_bn_bwd_apply': (c_int, [_P, _P, _P, _P, _P, ctypes.c_double, _P, c_int, c_int, c_int, c_float, _P]),
+    # dropout inside a block (layers.py:32-78, p > 0): the BatchNorm passes with the mask regenerated in them
+    'ms_dropout_bn_workspace': (c_size_t, [c_int, c_int, c_int]),
+    'ms_dropout_bn_fwd': (c_int, [_P] * 7 + [c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_int, ctypes.c_double, ctypes.c_uint32,
+                                  _P, _P, c_size_t, _P]),
+    'ms_dropout_bn_bwd': (c_int, [_P] * 7 + [c_int, c_int, c_int, c_float, c_float, c_int, c_int, ctypes.c_double, ctypes.c_uint32, _P, _P, c_size_t,
+                                  _P]),
+    'ms_dropout_advance': (c_int, [_P, _P]),
+    'ms_dropout_mask': (c_int, [_P, c_size_t, c_int, ctypes.c_double, ctypes.c_uint32, _P, _P]),
     'ms_lerp_time_fwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     'ms_lerp_time_bwd': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     'ms_softmax_mix_fwd': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),

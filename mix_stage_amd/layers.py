@@ -93,6 +93,27 @@ def frozen_batchnorm_blocks(root):
   return [m for m in root.modules() if isinstance(m, ConvNormRelu) and getattr(m, '_bn_frozen', False)]
 
 
+def dropout_blocks(root):
+  """The ConvNormRelu blocks under `root` constructed with p > 0, in modules() order."""
+  return [m for m in root.modules() if isinstance(m, ConvNormRelu) and m._p]
+
+
+def number_dropout_sites(root, state=None):
+  """Numbers the ConvNormRelu blocks under `root` for the dropout mask: a block's module id is its index among them in
+  modules() order (the `site` of a mask is module id + (visit << 20), include/mixstage.h).  Blocks with p == 0 are counted -- the
+  ids do not move when p changes -- but draw nothing.  state: the 4-word device state the blocks draw from (a trainer hands its
+  own); None leaves them on the process-wide default (mix_stage_amd.manual_dropout_seed).  The visit counts restart.
+  -> the number of blocks."""
+  n = 0
+  for m in root.modules():
+    if isinstance(m, ConvNormRelu):
+      if n >= (1 << 20):
+        raise ValueError('number_dropout_sites: more than 2^20 blocks')
+      m._drop_id, m._drop_visit, m._drop_state = n, 0, state
+      n += 1
+  return n
+
+
 # set to a list while a training step is being graph-captured: the ConvNormRelu blocks that ran with batch
 # statistics are recorded so graph replays can keep their num_batches_tracked counts right (train_step.py)
 _train_tape = None
@@ -172,7 +193,10 @@ class ConvNormRelu(nn.Module):
     self.relu = nn.LeakyReLU(negative_slope=0.2) if leaky else nn.ReLU()
     self._nd = 1 if type == '1d' else 2
     self._slope = 0.2 if leaky else 0.0
-    self._p = p
+    self._p = ops.check_dropout_p(p, 'ConvNormRelu(p=)')
+    # the dropout mask's site (p > 0, training): module id (number_dropout_sites, or a process-wide counter at first use), the
+    # draws since the step began, and the device state the mask is keyed with (None: the process-wide default)
+    self._drop_id, self._drop_visit, self._drop_state = None, 0, None
     self._geom = None
     # nn.BatchNorm's num_batches_tracked is kept as a host-side pending count and folded into the buffer
     # when the state is read: no per-layer device increment inside the (graph-captured) step.
@@ -205,7 +229,7 @@ class ConvNormRelu(nn.Module):
 
   def _run(self, x, x2=None, in_mode=MS_IN_PLAIN, out_f32=False, chain_prev=False, link=None):
     if self._p and self.training:
-      raise NotImplementedError('dropout p>0 is not on the Mix-StAGE path (p=0 everywhere, JL:26)')
+      return self._run_dropout(x, x2, in_mode, out_f32)
     n = self.norm
     frozen = bool(getattr(self, '_bn_frozen', False))
     if self.training and n.track_running_stats and not frozen:
@@ -243,6 +267,40 @@ class ConvNormRelu(nn.Module):
     return ops.conv_block(x, self.conv.weight, self.conv.bias, self._geometry(), mode, n.weight, n.bias,
                           n.running_mean, n.running_var, x2=x2, in_mode=in_mode,
                           chain_prev=chain_prev and (mode == MS_BN_TRAIN or frozen), link=link, frozen=frozen)
+
+  def _run_dropout(self, x, x2, in_mode, out_f32):
+    """Training mode with p > 0: conv (+bias) -> dropout(p) -> BatchNorm -> (Leaky)ReLU, the order of the reference (layers.py:65-70).
+    The conv is the block's MS_BARE launch (everything a bare block does holds: queued weight gradients, prepared data-gradient
+    weights, UP2ADD / BCAST inputs, bf16x6); dropout and BatchNorm are ops.dropout_bn_act, which regenerates the mask in its passes.
+    16-bit modes: the route of bn_sync='global' -- the conv leaves plain fp32 accumulators, the fp32 dropout kernels run on them,
+    and the activation goes back to 16 bits (two converter passes per dropout block)."""
+    if ops.bn_sync_active():
+      raise NotImplementedError("dropout p>0 with bn_sync='global' is not implemented (the statistics exchange has no masked form)")
+    n = self.norm
+    frozen = bool(getattr(self, '_bn_frozen', False)) or not n.track_running_stats
+    if not frozen:
+      self._note_train_pass()
+    if self._drop_id is None:
+      self._drop_id = ops.next_dropout_id()             # (stand-alone use: never numbered)
+    site = (self._drop_id + (self._drop_visit << 20)) & 0xffffffff
+    self._drop_visit += 1
+    g = self._geometry()
+    w = self.conv.weight
+    dt = getattr(self, '_ms_dt', 0)
+    if dt:
+      was_plain = not ops16.is_cb8(x)
+      if was_plain:
+        x = ops16.to_cb8(x, dt)
+        x2 = ops16.to_cb8(x2, dt) if x2 is not None else None
+      y_raw = ops16.conv_block16(x, w, self.conv.bias, g, MS_BARE, x2=x2, in_mode=in_mode, out_f32=True)
+    else:
+      y_raw = ops.conv_block(x, w, self.conv.bias, g, MS_BARE, x2=x2, in_mode=in_mode)
+    state = self._drop_state if self._drop_state is not None else ops.default_dropout_state(w.device)
+    y = ops.dropout_bn_act(y_raw, n.weight, n.bias, n.running_mean, n.running_var, g.slope, g.eps, g.momentum, self._p, site, state,
+                           channelwise=self._nd == 2, frozen=frozen)
+    if dt:
+      return y if (was_plain or out_f32) else ops16.to_cb8(y, dt)
+    return y
 
   def _next_desc(self, x):
     """The descriptor the fp32 block would run on the plain input x (ops.corun plans with it), None where that is not one launch."""
@@ -477,11 +535,12 @@ class PoseStyleEncoder(_TimeMajorStack):
   def forward_beside(self, x, host, host_x):
     """-> (host(host_x), self(x)): this encoder's blocks share the launches of `host`'s blocks (a UNet1D) where those leave compute
     units empty (ops.corun).  The two modules share no state, so every result is bit for bit what one after the other gives; it
-    stands aside -- exactly that order -- for the 16-bit and bf16x6 modes, bn_sync='global', CPU or float64 tensors, and whenever
-    a block of either module is hooked."""
+    stands aside -- exactly that order -- for the 16-bit and bf16x6 modes, bn_sync='global', CPU or float64 tensors, dropout p > 0 in
+    training mode, and whenever a block of either module is hooked."""
     blocks = [m for m in list(host.modules()) + list(self.modules()) if isinstance(m, ConvNormRelu)]
     if (getattr(self, '_ms_dt', 0) or getattr(host, '_ms_dt', 0) or ops16.is_cb8(host_x) or not ops.corun_ok(x, host_x)
-        or any(p.dtype != torch.float32 for p in self.parameters()) or _hooked(host, self, *blocks)):
+        or any(p.dtype != torch.float32 for p in self.parameters()) or _hooked(host, self, *blocks)
+        or any(b._p and b.training for b in blocks)):          # (dropout blocks are a bare conv + their own BatchNorm passes: no holds)
       out = host(host_x)
       return out, self(x)
     out, z = ops.corun(lambda: host(host_x), _chain_steps(self, x), x.device)

@@ -997,6 +997,163 @@ def sync_bn_act(y_raw, gamma, beta, running_mean, running_var, slope, eps, momen
 
 
 # ------------------------------------------------------------------------------------------------
+# Dropout inside a block (include/mixstage.h: ms_dropout_bn_fwd ...; layers.py:32-78 with p > 0).  The mask comes from a
+# counter-based generator inside the BatchNorm passes; what the device keeps is 4 int32 words (seed lo, seed hi, step, 0).
+_dropout = {'seed': 0, 'states': {}, 'next_id': 1 << 20}
+
+
+def check_dropout_p(p, who):
+  """A dropout probability as a float in [0, 1); ValueError otherwise (p == 1: BatchNorm of all zeros is meaningless)."""
+  try:
+    v = float(p)
+  except (TypeError, ValueError):
+    raise ValueError('%s: dropout p must be a float in [0, 1), got %r' % (who, p))
+  if not (v >= 0.0 and v < 1.0):
+    raise ValueError('%s: dropout p must be in [0, 1), got %r (p == 1 would leave BatchNorm nothing but zeros)' % (who, p))
+  return v
+
+
+def dropout_threshold(p):
+  """The keep rule of the mask: a value is kept iff its 32-bit word >= this (csrc/dropout_mask.h: dropout_threshold)."""
+  import math
+  return min(int(math.floor(check_dropout_p(p, 'dropout_threshold') * 4294967296.0 + 0.5)), 0xffffffff)
+
+
+def dropout_state_words(seed, step=0):
+  """(seed, step) -> the 4 int32 words of a dropout state as a host tensor: seed lo, seed hi, step, 0."""
+  seed, step = int(seed), int(step)
+  if not (0 <= seed < (1 << 64)) or not (0 <= step < (1 << 32)):
+    raise ValueError('dropout state: seed in [0, 2^64) and step in [0, 2^32), got %r, %r' % (seed, step))
+  words = torch.tensor([seed & 0xffffffff, seed >> 32, step, 0], dtype=torch.int64)
+  return torch.where(words >= (1 << 31), words - (1 << 32), words).to(torch.int32)
+
+
+def read_dropout_state(state):
+  """A device state -> dict(seed, step).  A synchronising host read."""
+  w = [int(v) & 0xffffffff for v in state.cpu().tolist()]
+  return dict(seed=w[0] | (w[1] << 32), step=w[2])
+
+
+def manual_dropout_seed(seed):
+  """The seed of the process-wide default dropout state, the one stand-alone modules draw their masks from (a trainer owns a
+  state of its own: MixStageTrainStep(dropout_seed=)).  The step word restarts at 0.  Not inside a capture.  The host generator
+  is not involved."""
+  words = dropout_state_words(seed, 0)
+  if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+    raise RuntimeError('manual_dropout_seed inside a stream capture')
+  _dropout['seed'] = int(seed)
+  for st in _dropout['states'].values():
+    st.copy_(words)
+  return int(seed)
+
+
+def default_dropout_state(device):
+  """The process-wide dropout state on `device` (made on first use from manual_dropout_seed's value)."""
+  key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+  st = _dropout['states'].get(key)
+  if st is None:
+    st = _dropout['states'][key] = dropout_state_words(_dropout['seed'], 0).to(device)
+  return st
+
+
+def next_dropout_id():
+  """A module id for a block nobody numbered (layers.number_dropout_sites): a process-wide counter that starts at 2^20."""
+  _dropout['next_id'] += 1
+  return _dropout['next_id'] - 1
+
+
+def _check_dropout_state(state, who):
+  if not (torch.is_tensor(state) and state.is_cuda and state.dtype == torch.int32 and state.is_contiguous() and state.numel() == 4):
+    raise TypeError('%s: the dropout state is a contiguous int32 device tensor of 4 words (seed lo, seed hi, step, 0)' % who)
+
+
+def dropout_advance(state):
+  """step += 1 on the device (one thread): the first launch of a training step whose blocks drop."""
+  _check_dropout_state(state, 'dropout_advance')
+  with torch.cuda.device(state.device):
+    check(lib().ms_dropout_advance(_ptr(state), _stream()), 'ms_dropout_advance')
+
+
+def dropout_mask(shape, p, site, state, channelwise=False):
+  """mask / (1 - p) of a block's conv output of `shape` (B, C, ...) as an fp32 tensor -- what the kernels regenerate in their
+  passes, written out for tests and reference implementations (ms_dropout_mask)."""
+  _check_dropout_state(state, 'dropout_mask')
+  p = check_dropout_p(p, 'dropout_mask')
+  out = torch.empty(tuple(shape), dtype=torch.float32, device=state.device)
+  inner = 1
+  if channelwise:
+    for v in shape[2:]:
+      inner *= int(v)
+  with torch.cuda.device(state.device):
+    check(lib().ms_dropout_mask(_ptr(out), out.numel(), inner, p, int(site) & 0xffffffff, _ptr(state), _stream()), 'ms_dropout_mask')
+  return out
+
+
+class _DropoutBNActFn(torch.autograd.Function):
+  @staticmethod
+  def forward(ctx, y_raw, gamma, beta, rm, rv, slope, eps, momentum, p, site, state, channelwise, frozen):
+    _need_hip(y_raw, gamma, beta, rm, rv)
+    y_raw = y_raw.contiguous()
+    B, C = y_raw.shape[0], y_raw.shape[1]
+    HW = y_raw.numel() // (B * C)
+    y = torch.empty_like(y_raw)
+    save = torch.empty(4 * C, dtype=torch.float32, device=y_raw.device)
+    L = lib()
+    need = L.ms_dropout_bn_workspace(B, C, HW)
+    ws = workspace(need, y_raw.device) if need else None
+    check(L.ms_dropout_bn_fwd(_ptr(y_raw), _ptr(gamma), _ptr(beta), _ptr(rm), _ptr(rv), _ptr(y), _ptr(save), B, C, HW, slope, eps, momentum,
+                              1 if frozen else 0, 1 if channelwise else 0, p, site, _ptr(state), _ptr(ws), ws.numel() if need else 0,
+                              _stream()), 'ms_dropout_bn_fwd')
+    ctx.save_for_backward(y_raw, gamma, save, state)
+    ctx.meta = (B, C, HW, slope, eps, p, site, channelwise, frozen)
+    ctx.params = (gamma, beta)
+    return y
+
+  @staticmethod
+  def backward(ctx, dy):
+    y_raw, gamma, save, state = ctx.saved_tensors
+    B, C, HW, slope, eps, p, site, channelwise, frozen = ctx.meta
+    dy = dy.contiguous()
+    pgamma, pbeta = ctx.params
+    affine = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+    dgamma = dbeta = None
+    direct_g = direct_b = True
+    if affine:
+      dgamma, direct_g = _grad_slot(pgamma, gamma)
+      dbeta, direct_b = _grad_slot(pbeta, gamma)
+    dyr = torch.empty_like(dy)
+    L = lib()
+    need = L.ms_dropout_bn_workspace(B, C, HW)
+    ws = workspace(need, dy.device) if need else None
+    # (the mask is regenerated from the state words as the step left them and the site this pass drew in its forward)
+    check(L.ms_dropout_bn_bwd(_ptr(dy), _ptr(y_raw), _ptr(save), _ptr(gamma), _ptr(dyr), _ptr(dgamma), _ptr(dbeta), B, C, HW, slope, eps,
+                              1 if frozen else 0, 1 if channelwise else 0, p, site, _ptr(state), _ptr(ws), ws.numel() if need else 0,
+                              _stream()), 'ms_dropout_bn_bwd')
+    return (dyr, None if direct_g else dgamma, None if direct_b else dbeta) + (None,) * 10
+
+
+def dropout_bn_act(y_raw, gamma, beta, running_mean, running_var, slope, eps, momentum, p, site, state, channelwise=False, frozen=False):
+  """dropout(p) -> BatchNorm -> LeakyReLU of a bare conv output, the mask regenerated inside the BatchNorm passes (no mask tensor;
+  y_raw stays undropped).  Batch statistics of the DROPPED values and a running-statistics update -- or, frozen, the running
+  statistics as they are.  site: module id + (visit << 20); state: the 4-word device state the mask is keyed with."""
+  p = check_dropout_p(p, 'dropout_bn_act')
+  if p == 0.0:
+    raise ValueError('dropout_bn_act: p == 0 is the plain block (conv_block with MS_BN_TRAIN / the frozen form)')
+  _check_dropout_state(state, 'dropout_bn_act')
+  args = (float(slope), float(eps), float(momentum), p, int(site) & 0xffffffff, state, bool(channelwise), bool(frozen))
+  if y_raw.dtype == torch.float64 or gamma.dtype == torch.float64:
+    # .double() model: the float64 boundary of conv_block
+    rm32, rv32 = _f32(running_mean), _f32(running_var)
+    y = _DropoutBNActFn.apply(_f32(y_raw), _f32(gamma), _f32(beta), rm32, rv32, *args)
+    if not frozen and running_mean.dtype == torch.float64:
+      with torch.no_grad():
+        running_mean.copy_(rm32)
+        running_var.copy_(rv32)
+    return y.double()
+  return _DropoutBNActFn.apply(y_raw, gamma, beta, running_mean, running_var, *args)
+
+
+# ------------------------------------------------------------------------------------------------
 # Chained pose decoder (include/mixstage.h: ms_decoder_chain_fwd): decoder.0-3 + logits + softmax mixture in one launch.
 CHAIN_SYNC_FIRST_WORD = 32             # (word 0 of the chain's sync buffer is the error flag: ops16.chain_sync)
 USE_DECODER_CHAIN = os.environ.get('MS_DECODER_CHAIN', '1') != '0'       # ablations: MS_DECODER_CHAIN=0 runs the blocks one by one

@@ -381,11 +381,18 @@ class MixStageTrainStep:
   names ('G.unet').  The ConvNormRelu blocks under them are flagged at construction (layers.freeze_batchnorm): they normalise with
   their running statistics whatever `training` says -- _ensure_train_mode is not involved --, never move them, and are
   differentiated.  The flags may change between steps (layers.freeze_batchnorm, or `_bn_frozen` set by hand): the set
-  of frozen blocks is part of the captured-graph key, a step under new flags is captured anew.  Composes with lr_schedule, ema_decay and on_bad_step."""
+  of frozen blocks is part of the captured-graph key, a step under new flags is captured anew.  Composes with lr_schedule, ema_decay and on_bad_step.
+
+  dropout_seed (only looked at when some ConvNormRelu block was built with p > 0; None: the process default,
+  mix_stage_amd.manual_dropout_seed): the trainer numbers the blocks of the model (layers.number_dropout_sites) and owns the 4-word
+  device state their masks are keyed with.  Every step, eager or captured, first launches the one-thread `advance`
+  that moves the state's step word, so each step -- each replay of a captured one -- draws fresh masks; the visit counts of the
+  blocks restart with the step (D runs twice in a D-step, on different masks).  dropout_state() / set_dropout_state() carry seed
+  and step for a resume that continues the mask sequence.  Without a p > 0 block nothing is allocated or launched."""
 
   def __init__(self, model, lr=1e-4, clip=1.0, use_graphs=True, process_group=None, time_steps=64, overlap_wgrad=False,
                bn_sync='local', overlap_allreduce=False, grad_buckets=None, grad_exchange='fp32', loss_scale=None, lr_schedule=None,
-               ema_decay=None, freeze_bn=None):
+               ema_decay=None, freeze_bn=None, dropout_seed=None):
     self.model = model
     # frozen BatchNorm statistics (fine-tuning): flags on the blocks, applied here; layers.freeze_batchnorm changes them later
     for root in layers.freeze_bn_roots(model, freeze_bn):
@@ -425,6 +432,14 @@ class MixStageTrainStep:
         raise NotImplementedError('fp16 training is single-rank: the data-parallel exchange of scaled gradients is not implemented')
       self.loss_scale_rule = LossScaleRule(loss_scale)
     self.process_group = process_group
+    # dropout (p > 0 blocks): sites numbered over the whole model, one device state for all of them; made below, next to the optimizers
+    self._dropout_state = None
+    self._dropout_blocks = layers.dropout_blocks(model)
+    if self._dropout_blocks:
+      if bn_sync == 'global':
+        raise NotImplementedError("dropout p>0 with bn_sync='global' is not implemented (the statistics exchange has no masked form)")
+      if _dp_world(process_group) > 1:
+        raise NotImplementedError('dropout p>0 is single-rank: data-parallel training with dropout is not implemented')
     if grad_exchange not in ('fp32', 'bf16'):
       raise ValueError("grad_exchange must be 'fp32' or 'bf16'")
     # 'bf16': the gradient all-reduce moves bf16 values (an option for the xGMI-bound exchange of the 16-bit mode; the optimizer
@@ -473,6 +488,10 @@ class MixStageTrainStep:
                             device_lr=self.lr_schedules is not None, ema_decay=self.ema_decay)
     self.optim_D = FlatAdam(model.D.parameters(), lr=lr, max_norm=clip, loss_scale=self.loss_scale_rule,
                             device_lr=self.lr_schedules is not None)
+    if self._dropout_blocks:
+      seed = ops._dropout['seed'] if dropout_seed is None else dropout_seed
+      self._dropout_state = ops.dropout_state_words(seed, 0).to(self.optim_G.flat_p.device)
+      layers.number_dropout_sites(model, self._dropout_state)
     self.use_graphs = use_graphs
     self.time_steps = time_steps
     self.pg = process_group
@@ -541,6 +560,12 @@ class MixStageTrainStep:
 
   def _forward_backward(self, audio, labels, pose, style, kind=None):
     m = self.model
+    if self._dropout_state is not None:
+      # fresh masks for this step: the visit counts restart (a site is module id + (visit << 20)) and the step word moves -- the
+      # first launch of the step, so a captured step moves it at every replay
+      for b in self._dropout_blocks:
+        b.__dict__['_drop_visit'] = 0
+      ops.dropout_advance(self._dropout_state)
     # the reference zeroes every gradient (trainer.py:604); only the network that steps receives gradients in a step (the
     # other one is frozen or runs under no_grad), and its buffer was zeroed before its own last step: one memset, not two
     if kind is None:
@@ -813,6 +838,8 @@ class MixStageTrainStep:
     if blocks is None:
       blocks = self._bn_blocks = [b for b in self.model.modules() if isinstance(b, layers.ConvNormRelu)]
     key = (k, pose_branch, tuple(audio.shape), tuple(pose.shape), tuple([b.__dict__.get('_bn_frozen', False) for b in blocks]))
+    if self._dropout_state is not None:
+      key = key + (tuple([b._p for b in self._dropout_blocks]),)       # (p is a by-value kernel argument of the captured launches)
     if self._static is None or self._static['key_shapes'] != key[2:4]:
       self._static = dict(key_shapes=key[2:4], audio=audio.clone(), labels=labels.clone(), pose=pose.clone(),
                           style=style.clone())
@@ -863,6 +890,7 @@ class MixStageTrainStep:
     rng = torch.get_rng_state()
     thresh = (m.G.thresh.value, m.G.thresh.iters)
     bn_state = {n: b.clone() for n, b in m.named_buffers()}
+    drop_state = self._dropout_state.clone() if self._dropout_state is not None else None
     # one eager pass on a side stream sizes the workspace and warms the allocator, then undo its side effects
     side = self._capture_stream
     side.wait_stream(torch.cuda.current_stream())
@@ -885,6 +913,8 @@ class MixStageTrainStep:
     with torch.no_grad():
       for n, b in m.named_buffers():
         b.copy_(bn_state[n])
+      if drop_state is not None:
+        self._dropout_state.copy_(drop_state)          # (the warm-up pass was a step of its own: its step word goes back)
     for mod in warm_tape:
       mod._pending_batches -= 1
     torch.set_rng_state(rng)
@@ -923,6 +953,21 @@ class MixStageTrainStep:
                  n_prepared=ops.prepared_count(opt.flat_p))
     self._graphs[key] = entry
     return entry
+
+  # ---- dropout ------------------------------------------------------------------------------------------------
+  def dropout_state(self):
+    """dict(seed, step) of the masks' device state (None without a p > 0 block): with set_dropout_state() a resumed run continues
+    the mask sequence.  A synchronising host read."""
+    return ops.read_dropout_state(self._dropout_state) if self._dropout_state is not None else None
+
+  def set_dropout_state(self, d):
+    """Write back what dropout_state() returned.  Between steps, not inside a capture: the captured steps read the words when
+    they replay."""
+    if self._dropout_state is None:
+      raise RuntimeError('MixStageTrainStep.set_dropout_state(): no ConvNormRelu block of the model has p > 0')
+    if torch.cuda.is_current_stream_capturing():
+      raise RuntimeError('MixStageTrainStep.set_dropout_state inside a stream capture')
+    self._dropout_state.copy_(ops.dropout_state_words(d['seed'], d['step']))
 
   # ---- learning rate ------------------------------------------------------------------------------------------
   def _lr_settable(self, who):
