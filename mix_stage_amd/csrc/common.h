@@ -92,6 +92,15 @@ __device__ inline float block_sum_256(float v, float* red) {
   __syncthreads();
   return red[0] + red[1] + red[2] + red[3];
 }
+// ... in double (`red` = 4 doubles of LDS).  The wave totals are added in pairs, not left to right as above: the order the sums of the
+// cross-rank BatchNorm backward (ms_bn_bwd_sums) and of the small dropout blocks have always had.
+__device__ inline double block_sum_256(double v, double* red) {
+  v = wave_sum_d(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
 
 // e / d for a wave-uniform divisor by multiply-high with floor(2^32 / d) + 1 (exact while e * d < 2^32, which `max_e` vouches
 // for; otherwise, and for d == 1, the plain division): the generic 32-bit division is ~25 instructions, and the small kernels'
@@ -171,6 +180,9 @@ __device__ inline float4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsi
   // (bit_cast of the whole vector: element-wise access of the builtin's result is miscompiled to a dword load by this clang)
   return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
 }
+
+// The four-word record of a BatchNorm channel, as `save` holds it (4 x C floats, one plane per word): bn_passes.h, frozen_bn()
+struct BNChannel { float mean, invstd, sc, sh; };
 
 // Running BatchNorm statistics (layers.py:60-66, momentum 0.1): a batch whose statistics are not finite -- the output of a launch
 // whose in-launch meeting timed out is poisoned with NaN, and every block downstream of it sees NaN -- must not reach the running

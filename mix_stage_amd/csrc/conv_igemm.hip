@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "bn_passes.h"
 #include "job_queue.h"
 
 namespace ms {
@@ -740,30 +741,19 @@ __global__ __launch_bounds__(256) void splitk_fwd_epilogue_kernel(const float* _
     }
     continue;
   }
-  const float mean = block_sum_256(s1, red) / (float)N;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < NE; ++i) {
-    const float d = v[i] - mean;
-    q += (t + i * 256 < N) ? d * d : 0.f;
-  }
-  const float m2 = block_sum_256(q, red);
-  const float var = m2 / (float)N;
-  const float invstd = 1.0f / sqrtf(var + eps);
-  const float sc = gamma[c] * invstd, sh = beta[c] - mean * sc;
+  const BNMoments<float> m = bn_reg_moments(v, s1, N, red);
+  const float var = bn_var(m, N);
+  const BNChannel bn = bn_channel(m, var, gamma, beta, c, eps);
   if (t == 0) {
-    save[c] = mean;
-    save[C + c] = invstd;
-    save[2 * C + c] = sc;
-    save[3 * C + c] = sh;
-    const float unbiased = N > 1 ? m2 / (float)(N - 1) : var;
-    running_stats_update(&rm[c], &rv[c], rm[c], rv[c], momentum, mean, unbiased);
+    bn_save_store(save, C, c, bn);
+    const float unbiased = bn_unbiased_var(m, N, var);
+    running_stats_update(&rm[c], &rv[c], rm[c], rv[c], momentum, bn.mean, unbiased);
   }
 #pragma unroll
   for (int i = 0; i < NE; ++i) {
     if (t + i * 256 < N) {
       y_raw[off[i]] = v[i];
-      y[off[i]] = lrelu(fmaf(v[i], sc, sh), slope);
+      y[off[i]] = lrelu(fmaf(v[i], bn.sc, bn.sh), slope);
     }
   }
   }
@@ -811,18 +801,15 @@ __global__ __launch_bounds__(256) void splitk_fwd_epilogue_big_kernel(const floa
     const float d = y_raw[((size_t)b * C + c) * HW + pix] - mean;   // written by this thread above
     q += d * d;
   }
-  const float m2 = block_sum_256(q, red);
-  const float var = m2 / (float)N;
-  const float invstd = 1.0f / sqrtf(var + eps);
-  sc = gamma[c] * invstd;
-  sh = beta[c] - mean * sc;
+  const BNMoments<float> m = {mean, block_sum_256(q, red)};
+  const float var = bn_var(m, N);
+  const BNChannel bn = bn_channel(m, var, gamma, beta, c, eps);
+  sc = bn.sc;
+  sh = bn.sh;
   if (t == 0) {
-    save[c] = mean;
-    save[C + c] = invstd;
-    save[2 * C + c] = sc;
-    save[3 * C + c] = sh;
-    const float unbiased = N > 1 ? m2 / (float)(N - 1) : var;
-    running_stats_update(&rm[c], &rv[c], rm[c], rv[c], momentum, mean, unbiased);
+    bn_save_store(save, C, c, bn);
+    const float unbiased = bn_unbiased_var(m, N, var);
+    running_stats_update(&rm[c], &rv[c], rm[c], rv[c], momentum, bn.mean, unbiased);
   }
   for (int e = t; e < N; e += 256) {
     const int b = e / HW, pix = e - b * HW;

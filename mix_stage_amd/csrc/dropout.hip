@@ -6,15 +6,20 @@
 //   backward  dz = dy * lrelu'(x * scale + shift), x_hat = (x - mean) * invstd,
 //             dy_raw = m * gamma * invstd * (dz - mean(dz) - x_hat * mean(dz * x_hat));  dgamma = sum dz * x_hat, dbeta = sum dz
 // FZ (frozen BatchNorm, layers.freeze_batchnorm): scale / shift come from the running statistics, which are only read, and the
-// backward drops the two batch-mean terms, as the FZ kernels of elementwise.hip do.
-// One workgroup owns a channel of at most 256 * 16 values and keeps them in registers (the forms of splitk_fwd_epilogue_kernel<NE>
-// and bn_bwd_fused_kernel<NE>); larger channels take two passes over chunks of batch items.  No workgroup waits for another; every
-// reduction runs in a fixed order (no float atomics): the same bits run to run, captured or eager.
+// backward drops the two batch-mean terms (bn_bwd_out<true>).
+// The channel arithmetic is that of bn_passes.h, shared with the forms without dropout; what is added here is the mask policy DropMask.
+//   one launch   one workgroup owns a channel of at most 256 * 16 values and keeps them in registers: dropout_bn_fwd_fused_kernel<NE>
+//                (bn_reg_moments + bn_channel, as splitk_fwd_epilogue_kernel<NE>) and dropout_bn_bwd_fused_kernel<NE> (bn_bwd_elem / bn_bwd_out)
+//   two passes   larger channels, over chunks of batch items: bn_stats_kernel<DropMask> + dropout_bn_apply_kernel (bn_combine_tiles +
+//                bn_channel) forward, bn_bwd_reduce_kernel<DropMask, float> + bn_bwd_apply_kernel<FZ, DropMask, false> backward -- the
+//                kernels of the plain block, instantiated with the mask
+// No workgroup waits for another; every reduction runs in a fixed order (no float atomics): the same bits run to run, captured or eager.
 #include <algorithm>
 
 #include <stdint.h>
 
 #include "kernels.h"
+#include "bn_passes.h"
 #include "dropout_mask.h"
 
 namespace ms {
@@ -43,14 +48,17 @@ __device__ __forceinline__ float dropout_in_loop(const DropoutArgs& da, const Dr
 // (a select, not a product: a dropped value is 0 whatever y_raw held)
 __device__ __forceinline__ float dropped(float v, float f) { return f != 0.f ? v * f : 0.f; }
 
-// block-wide sum in double for 256-thread blocks, in a fixed order; result valid in every thread.  `red` = 4 doubles of LDS.
-__device__ inline double block_sum_256_d(double v, double* red) {
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
+// the mask policy of bn_passes.h: x = dropped(y_raw, factor) wherever a value of y_raw is read, dy_raw masked with the same factor
+struct DropMask {
+  typedef DropoutArgs Args;
+  const DropoutArgs& da;
+  const DropoutSeed sd;
+  PlaneFactor pf = {-1, 0.f};      // the factor of the last (b, c) plane drawn: kept across a kernel's loops, redrawn when b changes
+  __device__ __forceinline__ explicit DropMask(const DropoutArgs& a) : da(a), sd(dropout_seed(a)) {}
+  __device__ __forceinline__ float factor(size_t off, int b, int C, int c) { return dropout_in_loop(da, sd, pf, off, b, C, c); }     // in a loop over b
+  __device__ __forceinline__ float factor_at(size_t off, int b, int C, int c) const { return dropout_of(da, sd, off, b, C, c); }   // anywhere
+  __device__ static __forceinline__ float apply(float v, float f) { return dropped(v, f); }
+};
 
 // ----------------------------------------------------------------------------------------------
 // forward, one launch: channels of at most 256 * NE values
@@ -63,7 +71,7 @@ __global__ __launch_bounds__(256) void dropout_bn_fwd_fused_kernel(const float* 
   const FastDiv fdHW(HW, B * HW);
   __shared__ float red[4];
   const int c = blockIdx.x, t = threadIdx.x, N = B * HW;
-  const DropoutSeed sd = dropout_seed(da);
+  const DropMask mask(da);
   float v[NE];
   size_t off[NE];
   // every load is issued before the first one is consumed (clamped indices instead of branches), the generator runs behind them
@@ -78,76 +86,34 @@ __global__ __launch_bounds__(256) void dropout_bn_fwd_fused_kernel(const float* 
 #pragma unroll
   for (int i = 0; i < NE; ++i) {
     const int e = min(t + i * 256, N - 1);
-    const float f = dropout_of(da, sd, off[i], fdHW.div(e), C, c);
-    v[i] = t + i * 256 < N ? dropped(v[i], f) : 0.f;
+    const float f = mask.factor_at(off[i], fdHW.div(e), C, c);
+    v[i] = t + i * 256 < N ? DropMask::apply(v[i], f) : 0.f;
     s1 += v[i];
   }
-  float mean, invstd, sc, sh;
+  BNChannel bn;
   if (FZ) {
-    const FrozenBN f = frozen_bn(gamma, beta, rm, rv, eps, c);
-    mean = f.mean; invstd = f.invstd; sc = f.sc; sh = f.sh;
-    if (t == 0) { save[c] = mean; save[C + c] = invstd; save[2 * C + c] = sc; save[3 * C + c] = sh; }
+    bn = frozen_bn(gamma, beta, rm, rv, eps, c);
+    if (t == 0) bn_save_store(save, C, c, bn);
   } else {
-    // (sum, M2 about the mean) in the order of splitk_fwd_epilogue_kernel
-    mean = block_sum_256(s1, red) / (float)N;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NE; ++i) {
-      const float d = v[i] - mean;
-      q += (t + i * 256 < N) ? d * d : 0.f;
-    }
-    const float m2 = block_sum_256(q, red);
-    const float var = m2 / (float)N;
-    invstd = 1.0f / sqrtf(var + eps);
-    sc = gamma[c] * invstd;
-    sh = beta[c] - mean * sc;
+    const BNMoments<float> m = bn_reg_moments(v, s1, N, red);
+    const float var = bn_var(m, N);
+    bn = bn_channel(m, var, gamma, beta, c, eps);
     if (t == 0) {
-      save[c] = mean; save[C + c] = invstd; save[2 * C + c] = sc; save[3 * C + c] = sh;
-      const float unbiased = N > 1 ? m2 / (float)(N - 1) : var;
-      running_stats_update(&rm[c], &rv[c], rm[c], rv[c], momentum, mean, unbiased);
+      bn_save_store(save, C, c, bn);
+      const float unbiased = bn_unbiased_var(m, N, var);
+      running_stats_update(&rm[c], &rv[c], rm[c], rv[c], momentum, bn.mean, unbiased);
     }
   }
 #pragma unroll
   for (int i = 0; i < NE; ++i)
-    if (t + i * 256 < N) y[off[i]] = lrelu(fmaf(v[i], sc, sh), slope);
+    if (t + i * 256 < N) y[off[i]] = lrelu(fmaf(v[i], bn.sc, bn.sh), slope);
 }
 
 // ----------------------------------------------------------------------------------------------
 // forward, two passes.  grid (C, nchunk); chunk = contiguous range of b_per_chunk batch items.
-// pass 1: stats[chunk][C][2] = (sum, M2 about the chunk's mean) of the dropped values -- the per-tile format bn_finalize_kernel combines
-__global__ __launch_bounds__(256) void dropout_bn_stats_kernel(const float* __restrict__ y_raw, float* __restrict__ stats, int B, int C,
-                                                               int HW, int b_per_chunk, const DropoutArgs da) {
-  prefetch_kernargs<128>();
-  __shared__ float red[4];
-  const int c = blockIdx.x, ch = blockIdx.y, t = threadIdx.x;
-  const int b0 = ch * b_per_chunk, nb = min(b_per_chunk, B - b0);
-  const int n = nb * HW;
-  const DropoutSeed sd = dropout_seed(da);
-  float s = 0.f;
-  PlaneFactor pf = {-1, 0.f};
-  for (int e = t; e < n; e += 256) {
-    const int b = b0 + e / HW, pix = e % HW;
-    const size_t off = ((size_t)b * C + c) * HW + pix;
-    s += dropped(y_raw[off], dropout_in_loop(da, sd, pf, off, b, C, c));
-  }
-  s = block_sum_256(s, red);
-  const float mean = s / (float)n;
-  float q = 0.f;
-  for (int e = t; e < n; e += 256) {
-    const int b = b0 + e / HW, pix = e % HW;
-    const size_t off = ((size_t)b * C + c) * HW + pix;
-    const float d = dropped(y_raw[off], dropout_in_loop(da, sd, pf, off, b, C, c)) - mean;
-    q += d * d;
-  }
-  q = block_sum_256(q, red);
-  if (t == 0) {
-    stats[((size_t)ch * C + c) * 2] = s;
-    stats[((size_t)ch * C + c) * 2 + 1] = q;
-  }
-}
-
-// pass 2: every workgroup combines the chunk partials of its channel itself, with the operations of bn_finalize_kernel in its order
-// (thread t takes chunks t, t + 256, ...); chunk 0 records `save` and moves the running statistics; all normalise their chunk.
+// pass 1: bn_stats_kernel<DropMask>.  pass 2: every workgroup combines the chunk partials of its channel itself (bn_combine_tiles: the
+// statistics of bn_finalize_kernel); chunk 0 records `save` and moves the running statistics; all normalise their chunk.  It is not
+// bn_finalize_apply_kernel with a mask: that one prefetches FA_PRE vectors of up to 16 bytes per thread, which the generator sits behind.
 // FZ: no pass 1, scale / shift from the running statistics.
 template <bool FZ>
 __global__ __launch_bounds__(256) void dropout_bn_apply_kernel(const float* __restrict__ y_raw, const float* __restrict__ stats,
@@ -159,57 +125,36 @@ __global__ __launch_bounds__(256) void dropout_bn_apply_kernel(const float* __re
   __shared__ double red[4];
   const int c = blockIdx.x, ch = blockIdx.y, t = threadIdx.x, nchunk = gridDim.y;
   const int N = B * HW;
-  float fmean, invstd, sc, sh;
+  BNChannel bn;
   if (FZ) {
-    const FrozenBN f = frozen_bn(gamma, beta, rm, rv, eps, c);
-    fmean = f.mean; invstd = f.invstd; sc = f.sc; sh = f.sh;
-    if (t == 0 && ch == 0) { save[c] = fmean; save[C + c] = invstd; save[2 * C + c] = sc; save[3 * C + c] = sh; }
+    bn = frozen_bn(gamma, beta, rm, rv, eps, c);
+    if (t == 0 && ch == 0) bn_save_store(save, C, c, bn);
   } else {
-    const int tile_n = b_per_chunk * HW;
-    double s = 0.0;
-    for (int i = t; i < nchunk; i += 256) s += (double)stats[((size_t)i * C + c) * 2];
-    s = wave_sum_d(s);
-    if ((t & 63) == 0) red[t >> 6] = s;
-    __syncthreads();
-    const double mean = (red[0] + red[1] + red[2] + red[3]) / (double)N;
-    __syncthreads();
-    double q = 0.0;
-    for (int i = t; i < nchunk; i += 256) {
-      const float* st = stats + ((size_t)i * C + c) * 2;
-      const int cnt = min(tile_n, N - i * tile_n);
-      const double d = (double)st[0] / (double)cnt - mean;
-      q += (double)st[1] + (double)cnt * d * d;
-    }
-    q = wave_sum_d(q);
-    if ((t & 63) == 0) red[t >> 6] = q;
-    __syncthreads();
-    const double m2 = red[0] + red[1] + red[2] + red[3];
-    const float var = (float)(m2 / (double)N);
-    invstd = 1.0f / sqrtf(var + eps);
-    fmean = (float)mean;
-    sc = gamma[c] * invstd;
-    sh = beta[c] - fmean * sc;
+    const BNMoments<double> m = bn_combine_tiles(stats, nullptr, nchunk, b_per_chunk * HW, N, C, c, red);
+    const float var = bn_var(m, N);
+    bn = bn_channel(m, var, gamma, beta, c, eps);
     if (t == 0 && ch == 0) {
-      save[c] = fmean; save[C + c] = invstd; save[2 * C + c] = sc; save[3 * C + c] = sh;
-      const float unbiased = N > 1 ? (float)(m2 / (double)(N - 1)) : var;
-      running_stats_update(&rm[c], &rv[c], rm[c], rv[c], momentum, fmean, unbiased);
+      bn_save_store(save, C, c, bn);
+      const float unbiased = bn_unbiased_var(m, N, var);
+      running_stats_update(&rm[c], &rv[c], rm[c], rv[c], momentum, bn.mean, unbiased);
     }
   }
   const int b0 = ch * b_per_chunk, nb = min(b_per_chunk, B - b0);
   const int n = nb * HW;
-  const DropoutSeed sd = dropout_seed(da);
-  PlaneFactor pf = {-1, 0.f};
+  DropMask mask(da);
   for (int e = t; e < n; e += 256) {
     const int b = b0 + e / HW, pix = e % HW;
     const size_t off = ((size_t)b * C + c) * HW + pix;
-    const float x = dropped(y_raw[off], dropout_in_loop(da, sd, pf, off, b, C, c));
-    y[off] = lrelu(fmaf(x, sc, sh), slope);
+    const float x = DropMask::apply(y_raw[off], mask.factor(off, b, C, c));
+    y[off] = lrelu(fmaf(x, bn.sc, bn.sh), slope);
   }
 }
 
 // ----------------------------------------------------------------------------------------------
-// backward, one launch: channels of at most 256 * NE values (bn_bwd_fused_kernel on the dropped values; the bias gradient is left
-// to the bare conv's backward, which sums dy_raw)
+// backward, one launch: channels of at most 256 * NE values (the element functions of bn_bwd_fused_kernel on the dropped values; the
+// bias gradient is left to the bare conv's backward, which sums dy_raw).  A kernel of its own, not bn_bwd_fused_kernel<NE, FZ, Mask>:
+// that one carries the inversion from the block's output y, the statistics groups and dbias, which a dropout block never has, and this
+// one the double path below; one kernel with all of it would be harder to read than the two.
 // The smallest instance (NE = 4, at most 1024 values per channel) takes the batch statistics again from the values in its registers
 // and carries them, x_hat and the two sums in double: with few values per channel dy_raw is what is left after two projections that
 // nearly cancel -- with TWO values x_hat is +-(1 - eps / 2 var) and dy_raw = gamma invstd (dz1 - dz2) / 2 * eps / (var + eps), a
@@ -225,8 +170,9 @@ __global__ __launch_bounds__(256) void dropout_bn_bwd_fused_kernel(const float* 
   __shared__ float red[4];
   __shared__ double redd[4];
   const int c = blockIdx.x, t = threadIdx.x, n = B * HW;
-  const DropoutSeed sd = dropout_seed(da);
-  const float mean = save[c], invstd = save[C + c], sc = save[2 * C + c], sh = save[3 * C + c], gm = gamma[c];
+  const DropMask mask(da);
+  const BNChannel bn = bn_save_load(save, C, c);
+  const float gm = gamma[c];
   float ry[NE], rg[NE], fm[NE];
   size_t ofs[NE];
 #pragma unroll
@@ -245,19 +191,19 @@ __global__ __launch_bounds__(256) void dropout_bn_bwd_fused_kernel(const float* 
     for (int i = 0; i < NE; ++i) {
       const bool ok = t + i * 256 < n;
       const int e = min(t + i * 256, n - 1);
-      fm[i] = dropout_of(da, sd, ofs[i], fdHW.div(e), C, c);
-      ry[i] = ok ? dropped(ry[i], fm[i]) : 0.f;                  // (x from here on)
-      dz[i] = ok ? rg[i] * (fmaf(ry[i], sc, sh) > 0.f ? 1.f : slope) : 0.f;
+      fm[i] = mask.factor_at(ofs[i], fdHW.div(e), C, c);
+      ry[i] = ok ? DropMask::apply(ry[i], fm[i]) : 0.f;                  // (x from here on)
+      dz[i] = ok ? bn_dz(rg[i], bn_act_pos(ry[i], bn), slope) : 0.f;
       xs += (double)ry[i];
     }
-    const double mean_d = block_sum_256_d(xs, redd) / (double)n;
+    const double mean_d = block_sum_256(xs, redd) / (double)n;
     double q = 0.0;
 #pragma unroll
     for (int i = 0; i < NE; ++i) {
       const double d = (double)ry[i] - mean_d;
       q += (t + i * 256 < n) ? d * d : 0.0;
     }
-    const double invstd_d = 1.0 / sqrt(block_sum_256_d(q, redd) / (double)n + (double)eps);
+    const double invstd_d = 1.0 / sqrt(block_sum_256(q, redd) / (double)n + (double)eps);
     double xhd[NE], d1 = 0.0, d2 = 0.0;
 #pragma unroll
     for (int i = 0; i < NE; ++i) {
@@ -265,12 +211,12 @@ __global__ __launch_bounds__(256) void dropout_bn_bwd_fused_kernel(const float* 
       d1 += (double)dz[i];
       d2 += (double)dz[i] * xhd[i];
     }
-    d1 = block_sum_256_d(d1, redd);
-    d2 = block_sum_256_d(d2, redd);
+    d1 = block_sum_256(d1, redd);
+    d2 = block_sum_256(d2, redd);
     const double gid = (double)gm * invstd_d, m1d = d1 / (double)n, m2d = d2 / (double)n;
 #pragma unroll
     for (int i = 0; i < NE; ++i)
-      if (t + i * 256 < n) dyr[ofs[i]] = dropped((float)(gid * ((double)dz[i] - m1d - xhd[i] * m2d)), fm[i]);
+      if (t + i * 256 < n) dyr[ofs[i]] = DropMask::apply((float)(gid * ((double)dz[i] - m1d - xhd[i] * m2d)), fm[i]);
     if (t == 0 && dgamma) { dgamma[c] = (float)d2; dbeta[c] = (float)d1; }
     return;
   }
@@ -278,88 +224,24 @@ __global__ __launch_bounds__(256) void dropout_bn_bwd_fused_kernel(const float* 
   for (int i = 0; i < NE; ++i) {
     const bool ok = t + i * 256 < n;
     const int e = min(t + i * 256, n - 1);
-    fm[i] = dropout_of(da, sd, ofs[i], fdHW.div(e), C, c);
-    const float x = dropped(ry[i], fm[i]);
-    const bool pos = fmaf(x, sc, sh) > 0.f;                 // (bit-identical to the forward pass)
-    dz[i] = ok ? rg[i] * (pos ? 1.f : slope) : 0.f;
-    xh[i] = ok ? (x - mean) * invstd : 0.f;
+    fm[i] = mask.factor_at(ofs[i], fdHW.div(e), C, c);
+    const BNBwdElem<float> el = bn_bwd_elem(DropMask::apply(ry[i], fm[i]), rg[i], bn, slope);
+    dz[i] = ok ? el.dz : 0.f;
+    xh[i] = ok ? el.xh : 0.f;
     s1 += dz[i];
     s2 += dz[i] * xh[i];
   }
   s1 = block_sum_256(s1, red);
   s2 = block_sum_256(s2, red);
   const float invN = 1.0f / (float)n;
-  const float gi = gm * invstd, m1 = s1 * invN, m2 = s2 * invN;
+  const float gi = gm * bn.invstd, m1 = s1 * invN, m2 = s2 * invN;
 #pragma unroll
-  for (int i = 0; i < NE; ++i) {
-    if (t + i * 256 < n) {
-      const float v = FZ ? gi * dz[i] : gi * (dz[i] - m1 - xh[i] * m2);
-      dyr[ofs[i]] = dropped(v, fm[i]);
-    }
-  }
+  for (int i = 0; i < NE; ++i)
+    if (t + i * 256 < n) dyr[ofs[i]] = DropMask::apply(bn_bwd_out<FZ>(gi, dz[i], m1, xh[i], m2), fm[i]);
   if (t == 0 && dgamma) { dgamma[c] = s2; dbeta[c] = s1; }
 }
 
-// backward, two passes (bn_bwd_reduce_kernel / bn_bwd_apply_kernel on the dropped values): partial[c][chunk] = (sum dz, sum dz * x_hat)
-__global__ __launch_bounds__(256) void dropout_bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ y_raw,
-                                                                    const float* __restrict__ save, float* __restrict__ partial, int B,
-                                                                    int C, int HW, int b_per_chunk, float slope, const DropoutArgs da) {
-  prefetch_kernargs<128>();
-  __shared__ float red[4];
-  const int c = blockIdx.x, ch = blockIdx.y, t = threadIdx.x;
-  const int b0 = ch * b_per_chunk, nb = min(b_per_chunk, B - b0);
-  const float mean = save[c], invstd = save[C + c], sc = save[2 * C + c], sh = save[3 * C + c];
-  const DropoutSeed sd = dropout_seed(da);
-  float s1 = 0.f, s2 = 0.f;
-  const int n = nb * HW;
-  PlaneFactor pf = {-1, 0.f};
-  for (int e = t; e < n; e += 256) {
-    const int b = b0 + e / HW, pix = e % HW;
-    const size_t off = ((size_t)b * C + c) * HW + pix;
-    const float x = dropped(y_raw[off], dropout_in_loop(da, sd, pf, off, b, C, c));
-    const float dz = dy[off] * (fmaf(x, sc, sh) > 0.f ? 1.f : slope);
-    s1 += dz;
-    s2 += dz * ((x - mean) * invstd);
-  }
-  s1 = block_sum_256(s1, red);
-  s2 = block_sum_256(s2, red);
-  if (t == 0) {
-    partial[((size_t)c * gridDim.y + ch) * 2] = s1;
-    partial[((size_t)c * gridDim.y + ch) * 2 + 1] = s2;
-  }
-}
-
-template <bool FZ>
-__global__ __launch_bounds__(256) void dropout_bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ y_raw,
-                                                                   const float* __restrict__ save, const float* __restrict__ gamma,
-                                                                   const float* __restrict__ partial, float* __restrict__ dyr,
-                                                                   float* dgamma, float* dbeta, int B, int C, int HW, int b_per_chunk,
-                                                                   float slope, const DropoutArgs da) {
-  prefetch_kernargs<128>();
-  const int c = blockIdx.x, ch = blockIdx.y, t = threadIdx.x, nchunk = gridDim.y;
-  float s1 = 0.f, s2 = 0.f;
-  for (int k = 0; k < nchunk; ++k) {
-    s1 += partial[((size_t)c * nchunk + k) * 2];
-    s2 += partial[((size_t)c * nchunk + k) * 2 + 1];
-  }
-  const float invN = 1.0f / (float)((size_t)B * HW);
-  const float mean = save[c], invstd = save[C + c], sc = save[2 * C + c], sh = save[3 * C + c];
-  const float gi = gamma[c] * invstd, m1 = s1 * invN, m2 = s2 * invN;
-  const int b0 = ch * b_per_chunk, nb = min(b_per_chunk, B - b0);
-  const int n = nb * HW;
-  const DropoutSeed sd = dropout_seed(da);
-  PlaneFactor pf = {-1, 0.f};
-  for (int e = t; e < n; e += 256) {
-    const int b = b0 + e / HW, pix = e % HW;
-    const size_t off = ((size_t)b * C + c) * HW + pix;
-    const float f = dropout_in_loop(da, sd, pf, off, b, C, c);
-    const float x = dropped(y_raw[off], f);
-    const float dz = dy[off] * (fmaf(x, sc, sh) > 0.f ? 1.f : slope);
-    const float xh = (x - mean) * invstd;
-    dyr[off] = dropped(FZ ? gi * dz : gi * (dz - m1 - xh * m2), f);
-  }
-  if (t == 0 && ch == 0 && dgamma) { dgamma[c] = s2; dbeta[c] = s1; }
-}
+// backward, two passes: bn_bwd_reduce_kernel<DropMask, float> and bn_bwd_apply_kernel<FZ, DropMask, false> of bn_passes.h
 
 // ----------------------------------------------------------------------------------------------
 // the step word moves once per training step (one thread: the first launch of the step, eager or captured)
@@ -404,11 +286,6 @@ size_t ms_dropout_bn_workspace(int B, int C, int HW) {
   return (size_t)bwd_chunks(B, C, &bpc) * C * 2 * sizeof(float);       // forward: chunk statistics; backward: chunk sums
 }
 
-#define MS_DROPOUT_FWD(N)                                                                                                        \
-  do {                                                                                                                           \
-    if (frozen) hipLaunchKernelGGL((dropout_bn_fwd_fused_kernel<N, true>), dim3(C), dim3(256), 0, s, y_raw, gamma, beta, running_mean, running_var, y, save, B, C, HW, slope, eps, momentum, da); \
-    else hipLaunchKernelGGL((dropout_bn_fwd_fused_kernel<N, false>), dim3(C), dim3(256), 0, s, y_raw, gamma, beta, running_mean, running_var, y, save, B, C, HW, slope, eps, momentum, da);      \
-  } while (0)
 int ms_dropout_bn_fwd(const float* y_raw, const float* gamma, const float* beta, float* running_mean, float* running_var, float* y,
                       float* save, int B, int C, int HW, float slope, float eps, float momentum, int frozen, int channelwise, double p,
                       uint32_t site, const int32_t* state, void* workspace, size_t workspace_bytes, void* stream) {
@@ -423,14 +300,15 @@ int ms_dropout_bn_fwd(const float* y_raw, const float* gamma, const float* beta,
     return set_error("ms_dropout_bn_fwd: workspace of %zu bytes, %zu needed (ms_dropout_bn_workspace)", workspace ? workspace_bytes : (size_t)0, need);
   const long n = (long)B * HW;
   if (n <= DROPOUT_FUSED_MAX) {
-    const int ne = n <= 256 * 4 ? 4 : n <= 256 * 8 ? 8 : 16;
+    const int ne = fused_ne(n);
     // (a frozen block's forward is a bn_apply, a batch-statistics block's a bn_finalize_apply: the families of the forms without dropout)
     TimingScope ts(s, 0, 8.0 * n * C, frozen ? "bn_apply fused<%d> C%d HW%d B%d frozen dropout" : "bn_finalize_apply<%d> C%d HW%d B%d fused dropout",
                    ne, C, HW, B);
     if (ts.skip()) return 0;
-    if (ne == 4) MS_DROPOUT_FWD(4);
-    else if (ne == 8) MS_DROPOUT_FWD(8);
-    else MS_DROPOUT_FWD(16);
+    launch_ne_fz(ne, frozen != 0, [&](auto NE, auto FZ) {
+      hipLaunchKernelGGL((dropout_bn_fwd_fused_kernel<decltype(NE)::value, decltype(FZ)::value>), dim3(C), dim3(256), 0, s, y_raw, gamma, beta,
+                         running_mean, running_var, y, save, B, C, HW, slope, eps, momentum, da);
+    });
     return check_launch("dropout_bn_fwd_fused_kernel");
   }
   int bpc;
@@ -444,19 +322,13 @@ int ms_dropout_bn_fwd(const float* y_raw, const float* gamma, const float* beta,
   }
   TimingScope ts(s, 0, 16.0 * n * C, "bn_finalize_apply<0> C%d HW%d B%d chunks%d dropout", C, HW, B, nchunk);
   if (ts.skip()) return 0;
-  hipLaunchKernelGGL(dropout_bn_stats_kernel, dim3(C, nchunk), dim3(256), 0, s, y_raw, (float*)workspace, B, C, HW, bpc, da);
-  if ((rc = check_launch("dropout_bn_stats_kernel"))) return rc;
+  hipLaunchKernelGGL(bn_stats_kernel<DropMask>, dim3(C, nchunk), dim3(256), 0, s, y_raw, (float*)workspace, B, C, HW, bpc, da);
+  if ((rc = check_launch("bn_stats_kernel"))) return rc;
   hipLaunchKernelGGL(dropout_bn_apply_kernel<false>, dim3(C, nchunk), dim3(256), 0, s, y_raw, (const float*)workspace, gamma, beta, running_mean,
                      running_var, y, save, B, C, HW, bpc, slope, eps, momentum, da);
   return check_launch("dropout_bn_apply_kernel");
 }
-#undef MS_DROPOUT_FWD
 
-#define MS_DROPOUT_BWD(N)                                                                                                        \
-  do {                                                                                                                           \
-    if (frozen) hipLaunchKernelGGL((dropout_bn_bwd_fused_kernel<N, true>), dim3(C), dim3(256), 0, s, dy, y_raw, save, gamma, dyr, dgamma, dbeta, B, C, HW, slope, eps, da); \
-    else hipLaunchKernelGGL((dropout_bn_bwd_fused_kernel<N, false>), dim3(C), dim3(256), 0, s, dy, y_raw, save, gamma, dyr, dgamma, dbeta, B, C, HW, slope, eps, da);      \
-  } while (0)
 int ms_dropout_bn_bwd(const float* dy, const float* y_raw, const float* save, const float* gamma, float* dyr, float* dgamma, float* dbeta,
                       int B, int C, int HW, float slope, float eps, int frozen, int channelwise, double p, uint32_t site,
                       const int32_t* state, void* workspace, size_t workspace_bytes, void* stream) {
@@ -472,29 +344,29 @@ int ms_dropout_bn_bwd(const float* dy, const float* y_raw, const float* save, co
     return set_error("ms_dropout_bn_bwd: workspace of %zu bytes, %zu needed (ms_dropout_bn_workspace)", workspace ? workspace_bytes : (size_t)0, need);
   const long n = (long)B * HW;
   if (n <= DROPOUT_FUSED_MAX) {
-    const int ne = n <= 256 * 4 ? 4 : n <= 256 * 8 ? 8 : 16;
+    const int ne = fused_ne(n);
     TimingScope ts(s, 0, 12.0 * n * C, "bn_bwd_fused<%d> C%d HW%d B%d%s dropout", ne, C, HW, B, frozen ? " frozen" : "");
     if (ts.skip()) return 0;
-    if (ne == 4) MS_DROPOUT_BWD(4);
-    else if (ne == 8) MS_DROPOUT_BWD(8);
-    else MS_DROPOUT_BWD(16);
+    launch_ne_fz(ne, frozen != 0, [&](auto NE, auto FZ) {
+      hipLaunchKernelGGL((dropout_bn_bwd_fused_kernel<decltype(NE)::value, decltype(FZ)::value>), dim3(C), dim3(256), 0, s, dy, y_raw, save, gamma,
+                         dyr, dgamma, dbeta, B, C, HW, slope, eps, da);
+    });
     return check_launch("dropout_bn_bwd_fused_kernel");
   }
   int bpc;
   const int nchunk = bwd_chunks(B, C, &bpc);
   TimingScope ts(s, 0, 20.0 * n * C, "bn_bwd(reduce+apply) C%d HW%d B%d%s dropout", C, HW, B, frozen ? " frozen" : "");
   if (ts.skip()) return 0;
-  hipLaunchKernelGGL(dropout_bn_bwd_reduce_kernel, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, (float*)workspace, B, C, HW, bpc, slope, da);
-  if ((rc = check_launch("dropout_bn_bwd_reduce_kernel"))) return rc;
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<DropMask, float>), dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, (float*)workspace, B, C, HW, bpc, slope, da);
+  if ((rc = check_launch("bn_bwd_reduce_kernel"))) return rc;
   if (frozen)
-    hipLaunchKernelGGL(dropout_bn_bwd_apply_kernel<true>, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, (const float*)workspace, dyr,
-                       dgamma, dbeta, B, C, HW, bpc, slope, da);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<true, DropMask, false>), dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, (const float*)workspace, dyr,
+                       (float*)nullptr, dgamma, dbeta, B, C, HW, bpc, slope, da);
   else
-    hipLaunchKernelGGL(dropout_bn_bwd_apply_kernel<false>, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, (const float*)workspace, dyr,
-                       dgamma, dbeta, B, C, HW, bpc, slope, da);
-  return check_launch("dropout_bn_bwd_apply_kernel");
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<false, DropMask, false>), dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, (const float*)workspace, dyr,
+                       (float*)nullptr, dgamma, dbeta, B, C, HW, bpc, slope, da);
+  return check_launch("bn_bwd_apply_kernel");
 }
-#undef MS_DROPOUT_BWD
 
 int ms_dropout_advance(int32_t* state, void* stream) {
   if (!state) return set_error("ms_dropout_advance: the dropout state is NULL");

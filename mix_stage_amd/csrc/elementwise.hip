@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "bn_passes.h"
 #include "conv16.h"
 #include "job_queue.h"
 
@@ -23,36 +24,14 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
                                                           float momentum) {
   prefetch_kernargs<128>();
   __shared__ double red[4];
-  const int c = blockIdx.x, t = threadIdx.x;
-  double s = 0.0;
-  for (int i = t; i < n_tiles; i += 256) s += (double)stats[((size_t)i * C + c) * 2];
-  s = wave_sum_d(s);
-  if ((t & 63) == 0) red[t >> 6] = s;
-  __syncthreads();
-  const double mean = (red[0] + red[1] + red[2] + red[3]) / (double)N;
-  __syncthreads();
-  double q = 0.0;
-  for (int i = t; i < n_tiles; i += 256) {
-    const float* st = stats + ((size_t)i * C + c) * 2;
-    const int cnt = counts ? (int)counts[i] : min(tile_n, N - i * tile_n);
-    const double d = (double)st[0] / (double)cnt - mean;
-    q += (double)st[1] + (double)cnt * d * d;
-  }
-  q = wave_sum_d(q);
-  if ((t & 63) == 0) red[t >> 6] = q;
-  __syncthreads();
-  if (t == 0) {
-    const double m2 = red[0] + red[1] + red[2] + red[3];
-    const float var = (float)(m2 / (double)N);
-    const float invstd = 1.0f / sqrtf(var + eps);
-    const float fmean = (float)mean;
-    const float sc = gamma[c] * invstd;
-    save[c] = fmean;
-    save[C + c] = invstd;
-    save[2 * C + c] = sc;
-    save[3 * C + c] = beta[c] - fmean * sc;
-    const float unbiased = N > 1 ? (float)(m2 / (double)(N - 1)) : var;
-    running_stats_update(&running_mean[c], &running_var[c], running_mean[c], running_var[c], momentum, fmean, unbiased);
+  const int c = blockIdx.x;
+  const BNMoments<double> m = bn_combine_tiles(stats, counts, n_tiles, tile_n, N, C, c, red);
+  if (threadIdx.x == 0) {
+    const float var = bn_var(m, N);
+    const BNChannel ch = bn_channel(m, var, gamma, beta, c, eps);
+    bn_save_store(save, C, c, ch);
+    const float unbiased = bn_unbiased_var(m, N, var);
+    running_stats_update(&running_mean[c], &running_var[c], running_mean[c], running_var[c], momentum, ch.mean, unbiased);
   }
 }
 
@@ -114,25 +93,19 @@ __global__ __launch_bounds__(256) void bn_finalize_apply_kernel(const float* __r
     if (t + 256 * j < n_tiles) {
       const int i = t + 256 * j;
       const int cnt = counts ? (int)cntf[j] : min(tile_n, N - i * tile_n);
-      const double d = (double)st[j].x / (double)cnt - mean;
-      q2 += (double)st[j].y + (double)cnt * d * d;
+      q2 += bn_tile_m2(st[j], cnt, mean);
     }
   q2 = wave_sum_d(q2);
   if ((t & 63) == 0) red[t >> 6] = q2;
   __syncthreads();
-  const double m2 = red[0] + red[1] + red[2] + red[3];
-  const float var = (float)(m2 / (double)N);
-  const float invstd = 1.0f / sqrtf(var + eps);
-  const float fmean = (float)mean;
-  const float sc = g * invstd;
-  const float sh = bt - fmean * sc;
+  const BNMoments<double> m = {mean, red[0] + red[1] + red[2] + red[3]};
+  const float var = bn_var(m, N);
+  const BNChannel bn = bn_channel(m, var, g, bt, eps);
+  const float sc = bn.sc, sh = bn.sh;
   if (t == 0 && ch == 0) {
-    save[c] = fmean;
-    save[C + c] = invstd;
-    save[2 * C + c] = sc;
-    save[3 * C + c] = sh;
-    const float unbiased = N > 1 ? (float)(m2 / (double)(N - 1)) : var;
-    running_stats_update(&running_mean[c], &running_var[c], rm, rv, momentum, fmean, unbiased);
+    bn_save_store(save, C, c, bn);
+    const float unbiased = bn_unbiased_var(m, N, var);
+    running_stats_update(&running_mean[c], &running_var[c], rm, rv, momentum, bn.mean, unbiased);
   }
   auto act = [&](vec_t u) {
 #pragma unroll
@@ -170,7 +143,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
   const float* shift = save + 3 * (size_t)C;
   if (FZ) {
     for (size_t c = (size_t)blockIdx.x * 256 + threadIdx.x; c < (size_t)C; c += (size_t)gridDim.x * 256) {
-      const FrozenBN f = frozen_bn(gamma, beta, rm, rv, eps, (int)c);
+      const BNChannel f = frozen_bn(gamma, beta, rm, rv, eps, (int)c);
       save[c] = f.mean;
       save[C + c] = f.invstd;
       save[2 * (size_t)C + c] = f.sc;
@@ -182,7 +155,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
       const int c = (int)(((i << 2) / HW) % C);
       float sc, sh;
-      if (FZ) { const FrozenBN f = frozen_bn(gamma, beta, rm, rv, eps, c); sc = f.sc; sh = f.sh; }
+      if (FZ) { const BNChannel f = frozen_bn(gamma, beta, rm, rv, eps, c); sc = f.sc; sh = f.sh; }
       else { sc = scale[c]; sh = shift[c]; }
       float4 v = reinterpret_cast<const float4*>(y_raw)[i];
       v.x = lrelu(fmaf(v.x, sc, sh), slope);
@@ -195,7 +168,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
       const int c = (int)((i / HW) % C);
       float sc, sh;
-      if (FZ) { const FrozenBN f = frozen_bn(gamma, beta, rm, rv, eps, c); sc = f.sc; sh = f.sh; }
+      if (FZ) { const BNChannel f = frozen_bn(gamma, beta, rm, rv, eps, c); sc = f.sc; sh = f.sh; }
       else { sc = scale[c]; sh = shift[c]; }
       y[i] = lrelu(fmaf(y_raw[i], sc, sh), slope);
     }
@@ -205,63 +178,9 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
 // ----------------------------------------------------------------------------------------------
 // Cross-rank ("global") BatchNorm, data parallel: the statistics of a block are exchanged between the ranks so that every
 // rank normalises with the statistics of the GLOBAL batch, like the single device the reference trains on (layers.py:65-70).
-// bn_stats: per channel (sum, M2 about the local mean) of y_raw -- the per-tile format bn_finalize_kernel combines, so the
-// all-gathered [world][C][2] array is finalized as `world` tiles of B*HW values each.
-__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ y_raw, float* __restrict__ out, int B, int C, int HW) {
-  __shared__ float red[4];
-  const int c = blockIdx.x, t = threadIdx.x, n = B * HW;
-  float s = 0.f;
-  for (int e = t; e < n; e += 256) {
-    const int b = e / HW, pix = e - b * HW;
-    s += y_raw[((size_t)b * C + c) * HW + pix];
-  }
-  s = block_sum_256(s, red);
-  const float mean = s / (float)n;
-  float q = 0.f;
-  for (int e = t; e < n; e += 256) {
-    const int b = e / HW, pix = e - b * HW;
-    const float d = y_raw[((size_t)b * C + c) * HW + pix] - mean;
-    q += d * d;
-  }
-  q = block_sum_256(q, red);
-  if (t == 0) { out[2 * c] = s; out[2 * c + 1] = q; }
-}
-
-// The stand-alone sums of the cross-rank BatchNorm (ms_bn_bwd_sums): (sum dz, sum dz*xhat) of this rank per channel, in two stages like
-// bn_bwd_reduce_kernel (grid (C, nchunk), chunk = contiguous range of batch items) but with the terms and every partial sum in double.
-// sum dz*xhat cancels (about sqrt(n) of n terms of size 1 remain): with fp32 terms and fp32 partials a single channel of 2047 values
-// came out 9e-7 off, more than four times what an fp32 evaluation on the host loses.  The activation mask still comes from the fp32
-// z = fma(y_raw, scale, shift), bit-identical to the forward pass.
-__global__ __launch_bounds__(256) void bn_bwd_reduce_wide_kernel(const float* __restrict__ dy, const float* __restrict__ y_raw,
-                                                                 const float* __restrict__ save, double* __restrict__ partial, int B,
-                                                                 int C, int HW, int b_per_chunk, float slope) {
-  __shared__ double red[8];
-  const int c = blockIdx.x, ch = blockIdx.y, t = threadIdx.x;
-  const int b0 = ch * b_per_chunk, nb = min(b_per_chunk, B - b0);
-  const float sc = save[2 * C + c], sh = save[3 * C + c];
-  const double mean = (double)save[c], invstd = (double)save[C + c];
-  double s1 = 0.0, s2 = 0.0;
-  const int n = nb * HW;
-  for (int e = t; e < n; e += 256) {
-    const int b = b0 + e / HW, pix = e % HW;
-    const size_t off = ((size_t)b * C + c) * HW + pix;
-    const float yr = y_raw[off];
-    const float z = fmaf(yr, sc, sh);
-    const double dz = (double)dy[off] * (z > 0.f ? 1.0 : (double)slope);
-    s1 += dz;
-    s2 += dz * (((double)yr - mean) * invstd);
-  }
-  s1 = wave_sum_d(s1);
-  s2 = wave_sum_d(s2);
-  if ((t & 63) == 0) { red[t >> 6] = s1; red[4 + (t >> 6)] = s2; }
-  __syncthreads();
-  if (t == 0) {
-    partial[((size_t)c * gridDim.y + ch) * 2] = (red[0] + red[1]) + (red[2] + red[3]);
-    partial[((size_t)c * gridDim.y + ch) * 2 + 1] = (red[4] + red[5]) + (red[6] + red[7]);
-  }
-}
-
-// sums the per-chunk partials of bn_bwd_reduce_wide_kernel (up to 1024 per channel when C = 1, added by one thread)
+// bn_stats (bn_stats_kernel<NoMask> with one chunk): per channel (sum, M2 about the local mean) of y_raw -- the per-tile format
+// bn_finalize_kernel combines, so the all-gathered [world][C][2] array is finalized as `world` tiles of B*HW values each.
+// The stand-alone backward sums (ms_bn_bwd_sums): bn_bwd_reduce_kernel<NoMask, double>, then its per-chunk partials summed (up to 1024 per channel when C = 1, added by one thread)
 __global__ void bn_bwd_sum_chunks_kernel(const double* __restrict__ partial, float* __restrict__ sums, int C, int nchunk) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
@@ -279,91 +198,20 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_sums_kernel(const float* __r
                                                                 const float* __restrict__ sums, float inv_n_global,
                                                                 float* __restrict__ dyr, int B, int C, int HW, float slope) {
   const int c = blockIdx.x, t = threadIdx.x, n = B * HW;
-  const float mean = save[c], invstd = save[C + c], sc = save[2 * C + c], sh = save[3 * C + c];
-  const float gi = gamma[c] * invstd, m1 = sums[2 * c] * inv_n_global, m2 = sums[2 * c + 1] * inv_n_global;
+  const BNChannel bn = bn_save_load(save, C, c);
+  const float gi = gamma[c] * bn.invstd, m1 = sums[2 * c] * inv_n_global, m2 = sums[2 * c + 1] * inv_n_global;
   for (int e = t + blockIdx.y * 256; e < n; e += 256 * gridDim.y) {
     const int b = e / HW, pix = e - b * HW;
     const size_t off = ((size_t)b * C + c) * HW + pix;
-    const float yr = y_raw[off];
-    const float z = fmaf(yr, sc, sh);
-    const float dz = dy[off] * (z > 0.f ? 1.f : slope);
-    dyr[off] = gi * (dz - m1 - (yr - mean) * invstd * m2);
+    const BNBwdElem<float> el = bn_bwd_elem(y_raw[off], dy[off], bn, slope);
+    dyr[off] = bn_bwd_out<false>(gi, el.dz, m1, el.xh, m2);
   }
 }
 
 // ----------------------------------------------------------------------------------------------
 // BatchNorm + LeakyReLU backward.  grid (C, nchunk); chunk = contiguous range of batch items.
-//   dz = dy * lrelu'(z), z = y_raw*scale+shift (bit-identical to forward);  xh = (y_raw-mean)*invstd
-//   partial[c][chunk] = (sum dz, sum dz*xh)
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ y_raw,
-                                                            const float* __restrict__ save, float* __restrict__ partial,
-                                                            int B, int C, int HW, int b_per_chunk, float slope) {
-  prefetch_kernargs<128>();
-  __shared__ float red[4];
-  const int c = blockIdx.x, ch = blockIdx.y, t = threadIdx.x;
-  const int b0 = ch * b_per_chunk, nb = min(b_per_chunk, B - b0);
-  const float mean = save[c], invstd = save[C + c], sc = save[2 * C + c], sh = save[3 * C + c];
-  float s1 = 0.f, s2 = 0.f;
-  const int n = nb * HW;
-  for (int e = t; e < n; e += 256) {
-    const int b = b0 + e / HW, pix = e % HW;
-    const size_t off = ((size_t)b * C + c) * HW + pix;
-    const float yr = y_raw[off];
-    const float z = fmaf(yr, sc, sh);
-    const float dz = dy[off] * (z > 0.f ? 1.f : slope);
-    s1 += dz;
-    s2 += dz * ((yr - mean) * invstd);
-  }
-  s1 = block_sum_256(s1, red);
-  s2 = block_sum_256(s2, red);
-  if (t == 0) {
-    partial[((size_t)c * gridDim.y + ch) * 2] = s1;
-    partial[((size_t)c * gridDim.y + ch) * 2 + 1] = s2;
-  }
-}
-
-//   dyr = gamma*invstd*(dz - s1/N - xh*s2/N);  colsum partial of dyr;  dgamma = s2, dbeta = s1
-// FZ (frozen BatchNorm: `save` holds the running statistics, which do not depend on the batch): dyr = gamma*invstd*dz -- the two
-// mean terms are the derivative of the batch statistics; same loads, same partial sums, same dgamma / dbeta
-template <bool FZ>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ y_raw,
-                                                           const float* __restrict__ save, const float* __restrict__ gamma,
-                                                           const float* __restrict__ partial, float* __restrict__ dyr,
-                                                           float* __restrict__ colpart, float* dgamma, float* dbeta,
-                                                           int B, int C, int HW, int b_per_chunk, float slope) {
-  prefetch_kernargs<128>();
-  __shared__ float red[4];
-  const int c = blockIdx.x, ch = blockIdx.y, t = threadIdx.x, nchunk = gridDim.y;
-  float s1 = 0.f, s2 = 0.f;
-  for (int k = 0; k < nchunk; ++k) {
-    s1 += partial[((size_t)c * nchunk + k) * 2];
-    s2 += partial[((size_t)c * nchunk + k) * 2 + 1];
-  }
-  const float invN = 1.0f / (float)((size_t)B * HW);
-  const float mean = save[c], invstd = save[C + c], sc = save[2 * C + c], sh = save[3 * C + c];
-  const float gi = gamma[c] * invstd, m1 = s1 * invN, m2 = s2 * invN;
-  const int b0 = ch * b_per_chunk, nb = min(b_per_chunk, B - b0);
-  const int n = nb * HW;
-  float cs = 0.f;
-  for (int e = t; e < n; e += 256) {
-    const int b = b0 + e / HW, pix = e % HW;
-    const size_t off = ((size_t)b * C + c) * HW + pix;
-    const float yr = y_raw[off];
-    const float z = fmaf(yr, sc, sh);
-    const float dz = dy[off] * (z > 0.f ? 1.f : slope);
-    const float xh = (yr - mean) * invstd;
-    const float v = FZ ? gi * dz : gi * (dz - m1 - xh * m2);
-    dyr[off] = v;
-    cs += v;
-  }
-  cs = block_sum_256(cs, red);
-  if (t == 0) {
-    colpart[(size_t)c * nchunk + ch] = cs;
-    if (ch == 0 && dgamma) { dgamma[c] = s2; dbeta[c] = s1; }
-  }
-}
-
-// The same two passes for rows of HW % 4 == 0 values: 16 bytes per lane and load, four pairs of loads in flight per thread (the
+// The scalar two passes are bn_bwd_reduce_kernel<NoMask, float> and bn_bwd_apply_kernel<FZ, NoMask, true> of bn_passes.h.
+// The two passes for rows of HW % 4 == 0 values: 16 bytes per lane and load, four pairs of loads in flight per thread (the
 // 2-D layers stream 70-330 MB through these two launches; one dword and two integer divisions per element ran at 3.5 TB/s).
 // `xsum` (C x chunks): the chunk's sum of x_hat -- the bias gradient is the sum of dy_raw = -gamma invstd mean(dz x_hat) sum(x_hat)
 // (zero but for rounding: a conv bias in front of BatchNorm), which the apply pass then writes itself: no column-sum partials of
@@ -375,7 +223,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce4_kernel(const float* __rest
   __shared__ float red[4];
   const int c = blockIdx.x, ch = blockIdx.y, t = threadIdx.x;
   const int b0 = ch * b_per_chunk, nb = min(b_per_chunk, B - b0);
-  const float mean = save[c], invstd = save[C + c], sc = save[2 * C + c], sh = save[3 * C + c];
+  const BNChannel bn = bn_save_load(save, C, c);
   const int HW4 = HW >> 2, nv = nb * HW4;
   const FastDiv fd(HW4, nv + 1024);
   float s1 = 0.f, s2 = 0.f, s3 = 0.f;
@@ -395,12 +243,10 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce4_kernel(const float* __rest
         const float a[4] = {yr[u].x, yr[u].y, yr[u].z, yr[u].w}, d[4] = {g[u].x, g[u].y, g[u].z, g[u].w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float z = fmaf(a[j], sc, sh);
-          const float dz = d[j] * (z > 0.f ? 1.f : slope);
-          const float xh = (a[j] - mean) * invstd;
-          s1 += dz;
-          s2 += dz * xh;
-          s3 += xh;
+          const BNBwdElem<float> el = bn_bwd_elem(a[j], d[j], bn, slope);
+          s1 += el.dz;
+          s2 += el.dz * el.xh;
+          s3 += el.xh;
         }
       }
     }
@@ -415,7 +261,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce4_kernel(const float* __rest
   }
 }
 
-template <bool FZ>     // (FZ: bn_bwd_apply_kernel)
+template <bool FZ>     // (FZ: bn_bwd_out)
 __global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* __restrict__ dy, const float* __restrict__ y_raw,
                                                             const float* __restrict__ save, const float* __restrict__ gamma,
                                                             const float* __restrict__ partial, float* __restrict__ dyr,
@@ -430,8 +276,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* __restr
     s3 += xsum[(size_t)c * nchunk + k];
   }
   const float invN = 1.0f / (float)((size_t)B * HW);
-  const float mean = save[c], invstd = save[C + c], sc = save[2 * C + c], sh = save[3 * C + c];
-  const float gi = gamma[c] * invstd, m1 = s1 * invN, m2 = s2 * invN;
+  const BNChannel bn = bn_save_load(save, C, c);
+  const float gi = gamma[c] * bn.invstd, m1 = s1 * invN, m2 = s2 * invN;
   const int b0 = ch * b_per_chunk, nb = min(b_per_chunk, B - b0);
   const int HW4 = HW >> 2, nv = nb * HW4;
   const FastDiv fd(HW4, nv + 1024);
@@ -453,10 +299,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* __restr
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float z = fmaf(a[j], sc, sh);
-          const float dz = d[j] * (z > 0.f ? 1.f : slope);
-          const float xh = (a[j] - mean) * invstd;
-          o[j] = FZ ? gi * dz : gi * (dz - m1 - xh * m2);
+          const BNBwdElem<float> el = bn_bwd_elem(a[j], d[j], bn, slope);
+          o[j] = bn_bwd_out<FZ>(gi, el.dz, m1, el.xh, m2);
         }
         *reinterpret_cast<float4*>(dyr + off[u]) = float4{o[0], o[1], o[2], o[3]};
       }
@@ -494,8 +338,9 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const float* __restri
            y_raw += (size_t)B * C * HW, y = y ? y + (size_t)B * C * HW : y) {
   // every load is issued before the first one is consumed (clamped indices instead of branches): the kernel pays one
   // memory round trip, not NE of them -- with one wave per SIMD nothing else hides that latency
-  const float mean = save[c], invstd = save[C + c], sc = save[2 * C + c], sh = save[3 * C + c], gm = gamma[c];
-  const bool from_y = !FZ && y != nullptr && !bn_inv_unsafe(mean, invstd, sc, sh, slope);       // (uniform: one channel per workgroup)
+  const BNChannel bn = bn_save_load(save, C, c);
+  const float gm = gamma[c];
+  const bool from_y = !FZ && y != nullptr && !bn_inv_unsafe(bn.mean, bn.invstd, bn.sc, bn.sh, slope);       // (uniform: one channel per workgroup)
   const float* src = from_y ? y : y_raw;
   float ry[NE], rg[NE];
   size_t ofs[NE];
@@ -507,7 +352,7 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const float* __restri
     ry[i] = src[ofs[i]];
     rg[i] = dy[ofs[i]];
   }
-  const float beta_c = fmaf(mean, sc, sh), inv_sl = 1.0f / slope, inv_g = invstd / sc;     // (from_y: slope, scale are not tiny)
+  const float beta_c = fmaf(bn.mean, bn.sc, bn.sh), inv_sl = 1.0f / slope, inv_g = bn.invstd / bn.sc;     // (from_y: slope, scale are not tiny)
   float dz[NE], xh[NE];
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -519,10 +364,10 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const float* __restri
       pos = ry[i] > 0.f;
       xv = ((pos ? ry[i] : ry[i] * inv_sl) - beta_c) * inv_g;
     } else {
-      pos = fmaf(ry[i], sc, sh) > 0.f;
-      xv = (ry[i] - mean) * invstd;
+      pos = bn_act_pos(ry[i], bn);
+      xv = bn_xhat(ry[i], bn);
     }
-    dz[i] = ok ? rg[i] * (pos ? 1.f : slope) : 0.f;
+    dz[i] = ok ? bn_dz(rg[i], pos, slope) : 0.f;
     xh[i] = ok ? xv : 0.f;
     s1 += dz[i];
     s2 += dz[i] * xh[i];
@@ -530,12 +375,12 @@ __global__ __launch_bounds__(256) void bn_bwd_fused_kernel(const float* __restri
   s1 = block_sum_256(s1, red);
   s2 = block_sum_256(s2, red);
   const float invN = 1.0f / (float)n;
-  const float gi = gm * invstd, m1 = s1 * invN, m2 = s2 * invN;
+  const float gi = gm * bn.invstd, m1 = s1 * invN, m2 = s2 * invN;
   float cs = 0.f;
 #pragma unroll
   for (int i = 0; i < NE; ++i) {
     if (t + i * 256 < n) {
-      const float v = FZ ? gi * dz[i] : gi * (dz[i] - m1 - xh[i] * m2);
+      const float v = bn_bwd_out<FZ>(gi, dz[i], m1, xh[i], m2);
       dyr[ofs[i]] = v;
       cs += v;
     }
@@ -564,8 +409,9 @@ __global__ __launch_bounds__(256) void bn_bwd_fused4_kernel(const float* __restr
   float tot_cs = 0.f, tot_s1 = 0.f, tot_s2 = 0.f;          // (sg statistics groups of B clips each: bn_bwd_fused_kernel)
   for (int grp = 0; grp < sg; ++grp, save += 4 * C, dy += (size_t)B * C * HW, dyr += (size_t)B * C * HW,
            y_raw += (size_t)B * C * HW, y = y ? y + (size_t)B * C * HW : y) {
-  const float mean = save[c], invstd = save[C + c], sc = save[2 * C + c], sh = save[3 * C + c], gm = gamma[c];
-  const bool from_y = !FZ && y != nullptr && !bn_inv_unsafe(mean, invstd, sc, sh, slope);       // (uniform: one channel per workgroup)
+  const BNChannel bn = bn_save_load(save, C, c);
+  const float gm = gamma[c];
+  const bool from_y = !FZ && y != nullptr && !bn_inv_unsafe(bn.mean, bn.invstd, bn.sc, bn.sh, slope);       // (uniform: one channel per workgroup)
   const float* src = from_y ? y : y_raw;
   float4 ry[NV], rg[NV];
   size_t ofs[NV];
@@ -577,7 +423,7 @@ __global__ __launch_bounds__(256) void bn_bwd_fused4_kernel(const float* __restr
     ry[i] = *reinterpret_cast<const float4*>(src + ofs[i]);
     rg[i] = *reinterpret_cast<const float4*>(dy + ofs[i]);
   }
-  const float beta_c = fmaf(mean, sc, sh), inv_sl = 1.0f / slope, inv_g = invstd / sc;     // (from_y: slope, scale are not tiny)
+  const float beta_c = fmaf(bn.mean, bn.sc, bn.sh), inv_sl = 1.0f / slope, inv_g = bn.invstd / bn.sc;     // (from_y: slope, scale are not tiny)
   float dz[NV][4], xh[NV][4];
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -592,10 +438,10 @@ __global__ __launch_bounds__(256) void bn_bwd_fused4_kernel(const float* __restr
         pos = a[j] > 0.f;
         xv = ((pos ? a[j] : a[j] * inv_sl) - beta_c) * inv_g;
       } else {
-        pos = fmaf(a[j], sc, sh) > 0.f;
-        xv = (a[j] - mean) * invstd;
+        pos = bn_act_pos(a[j], bn);
+        xv = bn_xhat(a[j], bn);
       }
-      dz[i][j] = ok ? g[j] * (pos ? 1.f : slope) : 0.f;
+      dz[i][j] = ok ? bn_dz(g[j], pos, slope) : 0.f;
       xh[i][j] = ok ? xv : 0.f;
       s1 += dz[i][j];
       s2 += dz[i][j] * xh[i][j];
@@ -604,14 +450,14 @@ __global__ __launch_bounds__(256) void bn_bwd_fused4_kernel(const float* __restr
   s1 = block_sum_256(s1, red);
   s2 = block_sum_256(s2, red);
   const float invN = 1.0f / (float)(B * HW);
-  const float gi = gm * invstd, m1 = s1 * invN, m2 = s2 * invN;
+  const float gi = gm * bn.invstd, m1 = s1 * invN, m2 = s2 * invN;
   float cs = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     if (t + i * 256 < nv) {
       float o[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { o[j] = FZ ? gi * dz[i][j] : gi * (dz[i][j] - m1 - xh[i][j] * m2); cs += o[j]; }
+      for (int j = 0; j < 4; ++j) { o[j] = bn_bwd_out<FZ>(gi, dz[i][j], m1, xh[i][j], m2); cs += o[j]; }
       *reinterpret_cast<float4*>(dyr + ofs[i]) = float4{o[0], o[1], o[2], o[3]};
     }
   }
@@ -1378,11 +1224,6 @@ int bwd_chunks(int B, int C, int* b_per_chunk) {
 
 // returns 1 if the fused single-launch form was used (dbias already final, no colsum_finalize needed)
 // frozen: `save` holds the running statistics (launch_bn_apply_frozen) -- the same forms, without the batch-statistics terms
-#define MS_BN_BWD_FUSED(KERNEL, N)                                                                                                \
-  do {                                                                                                                            \
-    if (frozen) hipLaunchKernelGGL((KERNEL<N, true>), dim3(C), dim3(256), 0, s, dy, y_raw, y, save, gamma, dyr, dbias, dgamma, dbeta, B, C, HW, slope, sg); \
-    else hipLaunchKernelGGL((KERNEL<N, false>), dim3(C), dim3(256), 0, s, dy, y_raw, y, save, gamma, dyr, dbias, dgamma, dbeta, B, C, HW, slope, sg);       \
-  } while (0)
 int launch_bn_bwd(const float* dy, const float* y_raw, const float* y, const float* save, const float* gamma, float* partial, float* dyr,
                   float* colpart, float* dbias, float* dgamma, float* dbeta, int B, int C, int HW, float slope, int* fused,
                   hipStream_t s, int sg, bool frozen) {
@@ -1394,16 +1235,16 @@ int launch_bn_bwd(const float* dy, const float* y_raw, const float* y, const flo
   if (n <= BN_BWD32_FUSED_MAX) {
     const bool vec4 = (HW & 3) == 0 && (((uintptr_t)dy | (uintptr_t)y_raw | (uintptr_t)y | (uintptr_t)dyr) & 15) == 0;
     // (the label names the kernel's form: "4" = the 16-byte kernel, <n> its template argument)
-    const int ne = vec4 ? (n <= 1024 ? 1 : n <= 2048 ? 2 : 4) : (n <= 256 * 4 ? 4 : n <= 256 * 8 ? 8 : 16);
-    TimingScope ts(s, 0, 12.0 * sg * B * C * HW, "bn_bwd_fused%s<%d> C%d HW%d B%d%s", vec4 ? "4" : "", ne, C, HW, B * sg,
+    const int ne = fused_ne(n);          // values per thread; the 16-byte kernels hold them as ne / 4 vectors
+    TimingScope ts(s, 0, 12.0 * sg * B * C * HW, "bn_bwd_fused%s<%d> C%d HW%d B%d%s", vec4 ? "4" : "", vec4 ? ne / 4 : ne, C, HW, B * sg,
                    frozen ? " frozen" : sg > 1 ? " pair" : "");
     if (ts.skip()) { *fused = 1; return 0; }
-    if (vec4 && n <= 1024) MS_BN_BWD_FUSED(bn_bwd_fused4_kernel, 1);
-    else if (vec4 && n <= 2048) MS_BN_BWD_FUSED(bn_bwd_fused4_kernel, 2);
-    else if (vec4) MS_BN_BWD_FUSED(bn_bwd_fused4_kernel, 4);
-    else if (n <= 256 * 4) MS_BN_BWD_FUSED(bn_bwd_fused_kernel, 4);
-    else if (n <= 256 * 8) MS_BN_BWD_FUSED(bn_bwd_fused_kernel, 8);
-    else MS_BN_BWD_FUSED(bn_bwd_fused_kernel, 16);
+    launch_ne_fz(ne, frozen, [&](auto NE, auto FZ) {
+      constexpr int ne_ = decltype(NE)::value;
+      constexpr bool fz = decltype(FZ)::value;
+      if (vec4) hipLaunchKernelGGL((bn_bwd_fused4_kernel<ne_ / 4, fz>), dim3(C), dim3(256), 0, s, dy, y_raw, y, save, gamma, dyr, dbias, dgamma, dbeta, B, C, HW, slope, sg);
+      else hipLaunchKernelGGL((bn_bwd_fused_kernel<ne_, fz>), dim3(C), dim3(256), 0, s, dy, y_raw, y, save, gamma, dyr, dbias, dgamma, dbeta, B, C, HW, slope, sg);
+    });
     *fused = 1;
     return check_launch("bn_bwd_fused_kernel");
   }
@@ -1414,7 +1255,7 @@ int launch_bn_bwd(const float* dy, const float* y_raw, const float* y, const flo
   if (ts.skip()) return 0;
   // (the reduce pass is the train form's as it is: the sums of dz and dz * x_hat are dbeta and dgamma in either form)
   if (vec) hipLaunchKernelGGL(bn_bwd_reduce4_kernel, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, partial, colpart, B, C, HW, bpc, slope);
-  else hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, partial, B, C, HW, bpc, slope);
+  else hipLaunchKernelGGL((bn_bwd_reduce_kernel<NoMask, float>), dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, partial, B, C, HW, bpc, slope, NoMask::Args());
   int rc = check_launch("bn_bwd_reduce_kernel");
   if (rc) return rc;
   if (vec) {
@@ -1427,15 +1268,14 @@ int launch_bn_bwd(const float* dy, const float* y_raw, const float* y, const flo
                          dgamma, dbeta, B, C, HW, bpc, slope);
     *fused = 1;
   } else if (frozen) {
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, partial, dyr, colpart,
-                       dgamma, dbeta, B, C, HW, bpc, slope);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<true, NoMask, true>), dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, partial, dyr, colpart,
+                       dgamma, dbeta, B, C, HW, bpc, slope, NoMask::Args());
   } else {
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, partial, dyr, colpart,
-                       dgamma, dbeta, B, C, HW, bpc, slope);
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<false, NoMask, true>), dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, gamma, partial, dyr, colpart,
+                       dgamma, dbeta, B, C, HW, bpc, slope, NoMask::Args());
   }
   return check_launch("bn_bwd_apply_kernel");
 }
-#undef MS_BN_BWD_FUSED
 
 // returns 1 in *fused when the bias gradient was written by this launch (no colsum_finalize needed)
 int launch_act_bwd(const float* dy, const float* y, float* dyr, float* colpart, float* dbias, int B, int C, int HW, int mode, float slope,
@@ -1443,12 +1283,13 @@ int launch_act_bwd(const float* dy, const float* y, float* dyr, float* colpart, 
   *fused = 0;
   const long nn = (long)B * HW;
   if (nn <= 256 * 16 && (mode == 1 || dbias)) {
-    TimingScope ts(s, 0, (mode == 1 ? 12.0 : 4.0) * B * C * HW, "act_bwd_fused<%d> C%d HW%d B%d mode%d", nn <= 256 * 4 ? 4 : nn <= 256 * 8 ? 8 : 16,
+    const int ne = fused_ne(nn);
+    TimingScope ts(s, 0, (mode == 1 ? 12.0 : 4.0) * B * C * HW, "act_bwd_fused<%d> C%d HW%d B%d mode%d", ne,
                    C, HW, B, mode);
     *fused = 1;
     if (ts.skip()) return 0;
-    if (nn <= 256 * 4) hipLaunchKernelGGL(act_bwd_fused_kernel<4>, dim3(C), dim3(256), 0, s, dy, y, dyr, dbias, B, C, HW, mode, slope);
-    else if (nn <= 256 * 8) hipLaunchKernelGGL(act_bwd_fused_kernel<8>, dim3(C), dim3(256), 0, s, dy, y, dyr, dbias, B, C, HW, mode, slope);
+    if (ne == 4) hipLaunchKernelGGL(act_bwd_fused_kernel<4>, dim3(C), dim3(256), 0, s, dy, y, dyr, dbias, B, C, HW, mode, slope);
+    else if (ne == 8) hipLaunchKernelGGL(act_bwd_fused_kernel<8>, dim3(C), dim3(256), 0, s, dy, y, dyr, dbias, B, C, HW, mode, slope);
     else hipLaunchKernelGGL(act_bwd_fused_kernel<16>, dim3(C), dim3(256), 0, s, dy, y, dyr, dbias, B, C, HW, mode, slope);
     return check_launch("act_bwd_fused_kernel");
   }
@@ -1523,7 +1364,7 @@ int ms_bn_stats(const float* y_raw, float* stats, int B, int C, int HW, void* st
   TimingScope ts((hipStream_t)stream, 0, 0, "ew|ew_bn_stats");
   if (ts.skip()) return 0;
   if (!y_raw || !stats || B < 1 || C < 1 || HW < 1) return set_error("ms_bn_stats: bad argument");
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, y_raw, stats, B, C, HW);
+  hipLaunchKernelGGL(bn_stats_kernel<NoMask>, dim3(C, 1), dim3(256), 0, (hipStream_t)stream, y_raw, stats, B, C, HW, B, NoMask::Args());
   return check_launch("bn_stats_kernel");
 }
 
@@ -1543,7 +1384,7 @@ int ms_bn_train_apply(const float* stats_all, int world, int n_local, const floa
 
 size_t ms_bn_bwd_workspace(int B, int C) {
   int bpc;
-  return (size_t)bwd_chunks(B, C, &bpc) * C * 2 * sizeof(double) + 256;        // double partials (bn_bwd_reduce_wide_kernel)
+  return (size_t)bwd_chunks(B, C, &bpc) * C * 2 * sizeof(double) + 256;        // double partials (bn_bwd_reduce_kernel<NoMask, double>)
 }
 
 int ms_bn_bwd_sums(const float* dy, const float* y_raw, const float* save, float* sums, int B, int C, int HW, float slope,
@@ -1555,7 +1396,8 @@ int ms_bn_bwd_sums(const float* dy, const float* y_raw, const float* save, float
   const int nchunk = bwd_chunks(B, C, &bpc);
   hipStream_t s = (hipStream_t)stream;
   if ((size_t)workspace & 7) return set_error("ms_bn_bwd_sums: the workspace must be 8-byte aligned");
-  hipLaunchKernelGGL(bn_bwd_reduce_wide_kernel, dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, (double*)workspace, B, C, HW, bpc, slope);
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<NoMask, double>), dim3(C, nchunk), dim3(256), 0, s, dy, y_raw, save, (double*)workspace, B, C, HW, bpc, slope,
+                     NoMask::Args());
   hipLaunchKernelGGL(bn_bwd_sum_chunks_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, (const double*)workspace, sums, C, nchunk);
   return check_launch("bn_bwd_sums kernels");
 }

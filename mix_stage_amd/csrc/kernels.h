@@ -1,5 +1,7 @@
 // Internal launcher interface shared by the translation units of libmixstage_hip.so.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace ms {
@@ -279,11 +281,11 @@ size_t dgrad_weight_elems(int groups, int Cog, int Cig, int KH, int KW, int SH, 
 int launch_bn_finalize(const float* stats, const float* counts, int n_tiles, int tile_n, int N, int C, const float* gamma,
                        const float* beta, float* rm, float* rv, float* save, float eps, float momentum, hipStream_t s);
 // mean | invstd | scale | shift of channel c from the RUNNING statistics, in fp32 with the operations of bn_finalize_kernel's last
-// step (frozen BatchNorm: the statistics are read, never written)
-struct FrozenBN { float mean, invstd, sc, sh; };
-__device__ __forceinline__ FrozenBN frozen_bn(const float* __restrict__ gamma, const float* __restrict__ beta,
+// step (frozen BatchNorm: the statistics are read, never written).  Its shift is one fma, not the train form's beta - mean * scale.
+using FrozenBN = BNChannel;       // (the name the 16-bit passes know it by)
+__device__ __forceinline__ BNChannel frozen_bn(const float* __restrict__ gamma, const float* __restrict__ beta,
                                               const float* __restrict__ rm, const float* __restrict__ rv, float eps, int c) {
-  FrozenBN f;
+  BNChannel f;
   f.mean = rm[c];
   f.invstd = 1.0f / sqrtf(rv[c] + eps);
   f.sc = gamma[c] * f.invstd;
@@ -300,6 +302,16 @@ int launch_bn_finalize_apply(const float* stats, const float* counts, int n_tile
                              const float* beta, float* rm, float* rv, float* save, float eps, float momentum, const float* y_raw,
                              float* y, int B, int HW, float slope, hipStream_t s);
 int bwd_chunks(int B, int C, int* b_per_chunk);
+// values per thread (NE) of the kernels in which one workgroup of 256 threads keeps a channel of n <= 256 * 16 values in registers
+inline int fused_ne(long n) { return n <= 256 * 4 ? 4 : n <= 256 * 8 ? 8 : 16; }
+// f(std::integral_constant<int, NE>, std::bool_constant<FZ>) for ne = 4, 8 or 16: the <NE, FZ> instance a launcher takes
+template <class F>
+inline void launch_ne_fz(int ne, bool frozen, F f) {
+  auto with_fz = [&](auto NE) { frozen ? f(NE, std::true_type()) : f(NE, std::false_type()); };
+  if (ne == 4) with_fz(std::integral_constant<int, 4>());
+  else if (ne == 8) with_fz(std::integral_constant<int, 8>());
+  else with_fz(std::integral_constant<int, 16>());
+}
 // values per channel (B * OH * OW) up to which BatchNorm backward is ONE launch that can take x_hat from the block's output y
 // (elementwise.hip: bn_bwd_fused*): the in-launch forward forms keep y_raw only where that inversion is unsafe
 constexpr int BN_BWD32_FUSED_MAX = 256 * 16;

@@ -25,7 +25,7 @@ EW_BLOCK_CAP = 2048            # E:1675 znorm, E:1720 / E:1732 concat, A:298 Ada
 ADAM_PER_BLOCK = 1024          # A:298
 CE_REG_MAX = 8                 # E:1069 `C <= 8`
 LP_PAIR_MAX = 2048             # E:1856
-BN_GY_MAX = 64                 # E:1653
+BN_GY_MAX = 64                 # E:1403
 COPY_MULTI_MAX = 8             # E:1888
 
 
@@ -38,7 +38,7 @@ def red_blocks(n):
 
 
 def bwd_chunks(B, C):
-  """-> (chunks launched, batch items per chunk, `want` before the cap by B)   (E:1466)"""
+  """-> (chunks launched, batch items per chunk, `want` before the cap by B)   (E:1210)"""
   want0 = 1 if C >= 1024 else cdiv(1024, C)
   want = max(1, min(want0, B))
   bpc = cdiv(B, want)
@@ -46,7 +46,7 @@ def bwd_chunks(B, C):
 
 
 def bn_apply_gy(B, HW):
-  return max(1, min(BN_GY_MAX, (B * HW + 2047) // 2048))        # E:1653
+  return max(1, min(BN_GY_MAX, (B * HW + 2047) // 2048))        # E:1403
 
 
 def mix_chunks(B, P, T):
@@ -216,7 +216,7 @@ for _C, _B, _HW, _world in [(1, 2047, 1, 1), (1, 8, 256, 2), (64, 32, 64, 1), (6
                             (1100, 5, 7, 2), (64, 32, 4096, 2), (7, 1, 2049, 1)]:
   _nchunk, _bpc, _want = bwd_chunks(_B, _C)
   _case('bn_c%d_b%d_hw%d_w%d' % (_C, _B, _HW, _world), 'bn_trio', _BN, _BN_S, 'lib', 'derived',
-        'want = %d batch chunks (E:1467) with B = %d %s it: %d chunks of %d; B * HW = %d gives gy = %d (E:1653); statistics of %d rank(s) (E:1623), n_global = %d * B * HW (E:1654)'
+        'want = %d batch chunks (E:1211) with B = %d %s it: %d chunks of %d; B * HW = %d gives gy = %d (E:1403); statistics of %d rank(s) (E:1372), n_global = %d * B * HW (E:1405)'
         % (_want, _B, 'below' if _B < _want else 'at' if _B == _want else 'above', _nchunk, _bpc, _B * _HW, bn_apply_gy(_B, _HW), _world, _world),
         claims=dict(want=_want, nchunk=_nchunk, bpc=_bpc, gy=bn_apply_gy(_B, _HW)), C=_C, B=_B, HW=_HW, world=_world)
 
