@@ -518,6 +518,31 @@ int ms_kmeans_labels(const float* pose, const int32_t* keep, const double* cente
 int ms_znorm_select(const float* x, const int32_t* keep, const double* mean, const double* inv_std, float* y, size_t rows,
                     int P, int PK, void* stream);
 
+/* Fitting what the pre-step consumes, on device (the reference fits once per speaker set with sklearn on the CPU: KMeans
+ * src/data/transform.py:247-427, ZNorm transform.py:99-244).  fp64 throughout, fixed summation order (bitwise reproducible for
+ * the same chunking), the caller owns every buffer.
+ * ms_kmeans_fit_accumulate: one chunk (B,T,P) of one Lloyd iteration.  The feature row (width W) and the nearest centre
+ *   (first minimum wins) are exactly those of ms_kmeans_labels.  labels (B,T) int64 is read and rewritten: rows whose label
+ *   differs from the one found there count as `changed` (fill with -1 before the first iteration).  state (fp64,
+ *   ms_kmeans_fit_state_elems = M*W + M + 2): sums[M][W] | counts[M] | inertia | changed -- ADDED to, chunk after chunk; zero it
+ *   at the start of an iteration.  workspace: ms_kmeans_fit_workspace(B*T, ...) bytes, contents unspecified on entry.
+ *   Refused before any launch: NULL pointers, feats outside 1..7, feats & 4 with odd PK, M < 1, a short workspace, M * (W + 1)
+ *   doubles beyond the 160 KiB of LDS a workgroup may declare, chunks of more than 2^30 rows (size functions return 0 then).
+ * ms_kmeans_fit_update: centres_out[m] = sums[m] / counts[m]; a cluster with count 0 keeps centres_in[m] (sklearn relocates
+ *   it: PARITY UNPINNED).  shift_out (4 doubles) = sum ||out - in||^2 | empty clusters | inertia | changed.
+ * ms_column_stats_accumulate: one chunk (rows, C) fp32 of ZNorm's statistics pass.  state (3*C doubles, zero at the start):
+ *   count[C] | mean[C] | M2[C]; a workgroup's slice gives a two-pass (mean, M2), slices join the state with Chan's update.
+ *   var = M2 / (count - ddof).  workspace: ms_column_stats_accumulate_workspace(rows, C) bytes. */
+size_t ms_kmeans_fit_workspace(int BT, int PK, int M, int feats);
+size_t ms_kmeans_fit_state_elems(int PK, int M, int feats);
+int ms_kmeans_fit_accumulate(const float* pose, const int32_t* keep, const double* centres, int64_t* labels, double* state,
+                             void* workspace, size_t workspace_bytes, int B, int T, int P, int PK, int M, int feats, void* stream);
+int ms_kmeans_fit_update(const double* state, const double* centres_in, double* centres_out, double* shift_out, int M, int W,
+                         void* stream);
+size_t ms_column_stats_accumulate_workspace(size_t rows, int C);
+int ms_column_stats_accumulate(const float* x, size_t rows, int C, double* state, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
 /* Step metrics ("next" row N3; src/evaluation/metrics.py:94-131,247-303 as called from trainer.py:865-915), on device:
  * per clip b, out[b][0] = sum |y - gt| over the kept columns (L1 numerator), out[b][1] = the same on first differences in
  * time (VelL1 numerator), out[b][2 + a*J + j] = number of time steps where joint j is within alphas[a] * max(h,w) of the

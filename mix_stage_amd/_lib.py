@@ -125,7 +125,14 @@ SIGNATURES = {
     'ms_softmax_mix_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     'ms_kmeans_labels': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     'ms_znorm_select': (c_int, [_P, _P, _P, _P, _P, c_size_t, c_int, c_int, _P]),
-    'ms_step_metrics': (c_int, [_P] * 7 + [c_int, _P, c_int, c_int, c_int, c_int, _P]),
+    # fitting the pre-step's centres and statistics (fit.py)
+    'ms_kmeans_fit_workspace': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'ms_kmeans_fit_state_elems': (c_size_t, [c_int, c_int, c_int]),
+    'ms_kmeans_fit_accumulate': (c_int, [_P] * 6 + [c_size_t] + [c_int] * 6 + [_P]),
+    'ms_kmeans_fit_update': (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
+    'ms_column_stats_accumulate_workspace': (c_size_t, [c_size_t, c_int]),
+    'ms_column_stats_accumulate': (c_int, [_P, c_size_t, c_int, _P, _P, c_size_t, _P]),
+    'ms_step_metrics':(c_int, [_P] * 7 + [c_int, _P, c_int, c_int, c_int, c_int, _P]),
     'ms_eval_accumulate': (c_int, [_P] * 8 + [c_int, c_int, c_int, c_int, ctypes.c_double, c_int, _P]),
     'ms_concat_style_fwd': (c_int, [_P, _P, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P]),
     'ms_concat_style_bwd': (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),

@@ -8,6 +8,7 @@
 
 #include "kernels.h"
 #include "bn_passes.h"
+#include "prestep_feat.h"
 #include "conv16.h"
 #include "job_queue.h"
 
@@ -705,41 +706,13 @@ __global__ void softmax_mix_bwd_finish_kernel(const float* __restrict__ soft, fl
 __global__ __launch_bounds__(256) void kmeans_labels_kernel(const float* __restrict__ pose, const int32_t* __restrict__ keep,
                                                             const double* __restrict__ centers, int64_t* __restrict__ labels,
                                                             int BT, int T, int P, int PK, int M, int feats) {
-  // feature blocks of KMeans.get_feats (transform.py:352-378), in its order: pose (PK) | velocity (PK) | speed (PK/2)
-  const bool f_pose = feats & 1, f_vel = feats & 2, f_speed = feats & 4;
-  const int o_vel = f_pose ? PK : 0, o_speed = o_vel + (f_vel ? PK : 0), D = o_speed + (f_speed ? PK / 2 : 0);
+  // feature blocks of KMeans.get_feats (transform.py:352-378), in its order: pose (PK) | velocity (PK) | speed (PK/2): prestep_feat.h
+  const KMFeat f(feats, PK);
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= BT) return;
-  const int t = r % T;
-  const float* xr = pose + (size_t)r * P;
-  int best = 0;
-  double bestd = 0.0;
-  for (int m = 0; m < M; ++m) {
-    const double* c = centers + (size_t)m * D;
-    double acc = 0.0;
-    if (f_pose | f_vel) {
-      for (int d = lane; d < PK; d += 64) {
-        const int col = keep[d];
-        const double x = (double)xr[col];
-        const double v = t > 0 ? x - (double)xr[col - P] : 0.0;
-        if (f_pose) { const double dx = c[d] - x; acc += dx * dx; }
-        if (f_vel) { const double dv = c[o_vel + d] - v; acc += dv * dv; }
-      }
-    }
-    if (f_speed) {
-      // speed of a joint = |(vx, vy)|: the x block and the y block of the kept columns are PK/2 apart
-      for (int d = lane; d < PK / 2; d += 64) {
-        const int cx = keep[d], cy = keep[PK / 2 + d];
-        const double vx = t > 0 ? (double)xr[cx] - (double)xr[cx - P] : 0.0;
-        const double vy = t > 0 ? (double)xr[cy] - (double)xr[cy - P] : 0.0;
-        const double ds = c[o_speed + d] - sqrt(vx * vx + vy * vy);
-        acc += ds * ds;
-      }
-    }
-    acc = wave_sum_d(acc);
-    if (m == 0 || acc < bestd) { bestd = acc; best = m; }
-  }
+  double bestd;
+  const int best = km_nearest_wave(f, pose + (size_t)r * P, keep, centers, M, lane, r % T, P, PK, &bestd);
   if (lane == 0) labels[r] = best;
 }
 
