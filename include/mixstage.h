@@ -518,6 +518,34 @@ int ms_kmeans_labels(const float* pose, const int32_t* keep, const double* cente
 int ms_znorm_select(const float* x, const int32_t* keep, const double* mean, const double* inv_std, float* y, size_t rows,
                     int P, int PK, void* stream);
 
+/* Device-resident clip store (clip_store.hip): the batch itself, drawn on the device -- gather B windows of T frames out of the raw
+ * rows of a whole speaker set and run the pre-step above on them in the same launch, bit for bit what ms_kmeans_labels and
+ * ms_znorm_select give on the gathered clips (km_nearest_wave and znorm_value of prestep_feat.h).  Never allocates, never
+ * synchronises: a HIP graph captures both entry points.
+ *   pose_rows (R, P), audio_rows (R, F)   fp32, all intervals concatenated frame by frame.  These two are exempt from the 2 GiB
+ *               limit of the other entry points: rows are addressed with 64-bit offsets from the plain pointers.
+ *   win_row (W) int64: first row of each window; win_style (W) int32.  A window whose rows are not all inside [0, R) is "no window".
+ *   order (n_order) int32: window ids in the order this epoch draws them.  n_order is a by-value argument, frozen into a captured
+ *               launch: a caller whose epochs differ in length passes the buffer's capacity and pads the tail with -1 (clip_store.py).
+ *   state       4 int32 device words: error flag | cursor into `order` | reserved 0 | reserved 0 -- read when the kernel RUNS.
+ *   clip b of the launch is window order[cursor + rank * B + b].  A position >= n_order, an entry < 0 or >= W is "no window": the
+ *               clip is written as zeros (label 0, style 0, index -1), state word 0 is set to 1 (sticky), and nothing is
+ *               dereferenced through the entry.
+ *   keep, centers (M, D), feats, the mean / inv_std vectors: as ms_kmeans_labels / ms_znorm_select take them, except that keep is
+ *               required here (the labels need it; PK == P takes the identity list).  `world` is only checked (0 <= rank < world):
+ *               the draw reads B positions from cursor + rank * B, the move by world * B is ms_clip_advance's.  Velocity is 0 at
+ *               the first frame of a WINDOW (t = frame within the window), whatever row precedes it in the store.
+ *   out         audio (B,T,F) fp32 z-normed | labels (B,T) int64 | y (B,T,PK) fp32 z-normed kept columns | style (B,T) int64, the
+ *               window's style id on every frame | pose_full_norm (B,T,P) fp32 z-normed full pose, or NULL | indices (B) int32.
+ * ms_clip_advance: one thread, state[1] += step (world * B after a draw), stream-ordered behind the draw's reads: a replayed graph
+ *   of draw + advance moves through the order without the host. */
+int ms_clip_draw(const float* pose_rows, const float* audio_rows, int64_t R, const int64_t* win_row, const int32_t* win_style, int W,
+                 const int32_t* order, int n_order, int32_t* state, int B, int T, int rank, int world,
+                 const int32_t* keep, const double* centers, int M, int feats, const double* pose_mean, const double* pose_inv_std,
+                 const double* audio_mean, const double* audio_inv_std, int P, int PK, int F, float* audio, int64_t* labels, float* y,
+                 int64_t* style, float* pose_full_norm, int32_t* indices, void* stream);
+int ms_clip_advance(int32_t* state, int step, void* stream);
+
 /* Fitting what the pre-step consumes, on device (the reference fits once per speaker set with sklearn on the CPU: KMeans
  * src/data/transform.py:247-427, ZNorm transform.py:99-244).  fp64 throughout, fixed summation order (bitwise reproducible for
  * the same chunking), the caller owns every buffer.

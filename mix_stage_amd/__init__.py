@@ -14,9 +14,11 @@ from .gan import GAN  # noqa: F401
 from .lr_schedule import ConstantLR, ExponentialLR, as_lr_schedule  # noqa: F401
 from .prestep import DevicePreStep  # noqa: F401
 from .fit import DeviceColumnStats, DeviceKMeansFit  # noqa: F401
+from .clip_store import DeviceClipStore, epoch_order, steps_per_epoch, window_table  # noqa: F401
 
 __all__ = ['ConvNormRelu', 'UNet1D', 'AudioEncoder', 'PoseEncoder', 'PoseStyleEncoder', 'TextEncoder1D',
            'ClusterClassify', 'Group', 'EmbLin', 'Curriculum', 'JointLateClusterSoftStyle4_G',
            'JointLateClusterSoftStyle4_D', 'Speech2Gesture_D', 'GAN', 'set_compute_dtype', 'set_inference_folding',
            'compute_dtype', 'freeze_batchnorm', 'frozen_batchnorm_blocks', 'ExponentialLR', 'ConstantLR', 'as_lr_schedule',
-           'number_dropout_sites', 'manual_dropout_seed', 'DevicePreStep', 'DeviceKMeansFit', 'DeviceColumnStats']
+           'number_dropout_sites', 'manual_dropout_seed', 'DevicePreStep', 'DeviceKMeansFit', 'DeviceColumnStats',
+           'DeviceClipStore', 'window_table', 'epoch_order', 'steps_per_epoch']

@@ -125,6 +125,10 @@ SIGNATURES = {
     'ms_softmax_mix_bwd': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     'ms_kmeans_labels': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     'ms_znorm_select': (c_int, [_P, _P, _P, _P, _P, c_size_t, c_int, c_int, _P]),
+    # the device-resident clip store (clip_store.py): draw a batch on the device, move the cursor
+    'ms_clip_draw': (c_int, [_P, _P, ctypes.c_int64, _P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int,
+                             _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    'ms_clip_advance': (c_int, [_P, c_int, _P]),
     # fitting the pre-step's centres and statistics (fit.py)
     'ms_kmeans_fit_workspace': (c_size_t, [c_int, c_int, c_int, c_int]),
     'ms_kmeans_fit_state_elems': (c_size_t, [c_int, c_int, c_int]),

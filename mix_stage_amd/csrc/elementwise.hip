@@ -724,7 +724,7 @@ __global__ __launch_bounds__(256) void znorm_select_kernel(const float* __restri
     const size_t r = i / PK;
     const int d = (int)(i - r * PK);
     const int col = keep ? keep[d] : d;
-    y[i] = (float)(((double)x[r * P + col] - mean[col]) * inv_std[col]);
+    y[i] = znorm_value(x[r * P + col], mean[col], inv_std[col]);
   }
 }
 

@@ -97,4 +97,8 @@ __device__ __forceinline__ int km_nearest_wave(const KMFeat& f, const float* __r
   return best;
 }
 
+// ZNorm of one value (transform.py:221-226), in fp64 with the reciprocal of the standard deviation, rounded once to fp32.
+// ms_znorm_select (elementwise.hip) and the clip store's draw (clip_store.hip) both call this, so their bits agree by construction.
+__device__ __forceinline__ float znorm_value(float x, double mean, double inv_std) { return (float)(((double)x - mean) * inv_std); }
+
 }  // namespace ms

@@ -558,8 +558,10 @@ class MixStageTrainStep:
     return dict(input_modalities=self.model.input_modalities, desc='train', sample_flag=0, description='train',
                 style=style, time_steps=self.time_steps)
 
-  def _forward_backward(self, audio, labels, pose, style, kind=None):
+  def _forward_backward(self, audio, labels, pose, style, kind=None, head=None):
     m = self.model
+    if head is not None:
+      head()          # step_from: the draw's launches fill the four input buffers -- the head of the step, eager or captured
     if self._dropout_state is not None:
       # fresh masks for this step: the visit counts restart (a site is module id + (visit << 20)) and the step word moves -- the
       # first launch of the step, so a captured step moves it at every replay
@@ -717,6 +719,38 @@ class MixStageTrainStep:
     With lr_schedule: the step reads its optimizer's learning-rate word when it runs.  ORDERING RULE: epoch_end() / set_lr() write
     the words on the caller's current stream, the stream step() launches or replays on -- call them between two steps, from the
     thread and under the stream that calls step(); stream order does the rest (no synchronisation)."""
+    return self._step(kind, (audio, labels, pose, style), None, inputs_unchanged)
+
+  def step_from(self, store, prestep, kind=None, B=None):
+    """One training step on the next B windows of a DeviceClipStore (clip_store.py), pre-processed by `prestep` as
+    DevicePreStep.__call__ would: the same step, bit for bit, as step(*store.draw(prestep, B), kind=kind).  B defaults to the
+    store's batch_size.  Data parallel: every rank builds the same store with the same seed and its own rank (shard(), or
+    DeviceClipStore(..., trainer=ts)) and draws its own B of each world * B; a store whose rank / world are not this trainer's is
+    refused with ValueError.
+    Graph mode: the draw's two launches are the head of the captured step and write into its static input buffers -- no input copy,
+    no pre-step launches, one replay is the whole step, data included; store.new_epoch() between steps needs no re-capture.
+    Raises IndexError past the end of the epoch's order before anything is launched (store.steps_left counts the steps)."""
+    from .clip_store import StoreFeed
+    if (store.rank, store.world) != self.shard():
+      raise ValueError('MixStageTrainStep.step_from: the store draws as rank %d of %d, this trainer is rank %d of %d: build it with '
+                       'trainer=ts (or rank / world of ts.shard())' % ((store.rank, store.world) + self.shard()))
+    B = store.batch_size if B is None else B
+    if B is None:
+      raise ValueError('MixStageTrainStep.step_from: give B, or build the store with batch_size')
+    feed = StoreFeed(store, prestep, B)
+    if self._in_ema_weights:
+      raise RuntimeError('MixStageTrainStep.step_from() inside ema_weights(): the parameters hold the average, leave the context first')
+    store._room(feed.B)             # (the host mirror moves where the draw is issued: feed.draw() here, the replay in _graph_step)
+    if not self.use_graphs:
+      return self._step(kind, feed.draw(), None, False)
+    return self._step(kind, None, feed, False)
+
+  def shard(self):
+    """(rank, world) of this trainer's data-parallel job: what a DeviceClipStore of this process is built with."""
+    return (dist.get_rank(self.pg) if self.world > 1 else 0, self.world)
+
+  def _step(self, kind, inputs, feed, inputs_unchanged):
+    """step() on four tensors (`inputs`) or, graph mode only, on a store's draw captured with the step (`feed`)."""
     m = self.model
     if self._in_ema_weights:
       raise RuntimeError('MixStageTrainStep.step() inside ema_weights(): the parameters hold the average, leave the context first')
@@ -732,7 +766,7 @@ class MixStageTrainStep:
       self.optim_D.resync_if_modified()
       if not self.use_graphs:
         m._lambda_host_writes = True        # (eager: forward() refreshes the device-side loss weights itself)
-        self.fake_pose, self.losses = self._with_marker(self._forward_backward, audio, labels, pose, style, k)
+        self.fake_pose, self.losses = self._with_marker(self._forward_backward, *inputs, k)
         opt = self.optim_G if m.G_flag else self.optim_D
         active = opt.active_params()
         opt.mark_active(active)
@@ -740,7 +774,7 @@ class MixStageTrainStep:
         self._refresh_meetings()
         opt.clip_and_step()
       else:
-        self._graph_step(k, pose_branch, audio, labels, pose, style, inputs_unchanged)
+        self._graph_step(k, pose_branch, inputs, inputs_unchanged, feed)
     finally:
       if kind is not None:
         m.D_prob = saved
@@ -830,23 +864,32 @@ class MixStageTrainStep:
       self._health_seen = count         # (counters zeroed by FlatAdam.reset_state since the last look)
     ops16.check_meetings()                  # a meeting that expired outside a training step (e.g. an evaluation forward)
 
-  def _graph_step(self, k, pose_branch, audio, labels, pose, style, inputs_unchanged=False):
+  def _graph_step(self, k, pose_branch, inputs, inputs_unchanged=False, feed=None):
+    """inputs: the caller's (audio, labels, pose, style), copied into the static buffers -- or feed (step_from): the store's draw is
+    the head of the captured step and fills them itself."""
     self.model._lambda_host_writes = False   # the captured loss kernels read the device tensor written below
+    shapes = feed.shapes if feed is not None else (tuple(inputs[0].shape), tuple(inputs[2].shape))
     # (the set of frozen-BatchNorm blocks is part of the key: a captured step holds the launches of the flags it was captured with.
     # The flags are plain attributes anybody may set: they are read every step, ~50 dictionary look-ups)
     blocks = self._bn_blocks
     if blocks is None:
       blocks = self._bn_blocks = [b for b in self.model.modules() if isinstance(b, layers.ConvNormRelu)]
-    key = (k, pose_branch, tuple(audio.shape), tuple(pose.shape), tuple([b.__dict__.get('_bn_frozen', False) for b in blocks]))
+    key = (k, pose_branch, shapes[0], shapes[1], tuple([b.__dict__.get('_bn_frozen', False) for b in blocks]))
     if self._dropout_state is not None:
       key = key + (tuple([b._p for b in self._dropout_blocks]),)       # (p is a by-value kernel argument of the captured launches)
-    if self._static is None or self._static['key_shapes'] != key[2:4]:
-      self._static = dict(key_shapes=key[2:4], audio=audio.clone(), labels=labels.clone(), pose=pose.clone(),
-                          style=style.clone())
+    if feed is not None:
+      key = key + (feed.key,)       # (the store, the pre-step and B: pointers and by-value arguments of the captured draw)
+    if self._static is None or self._static['key_shapes'] != key[2:4] or (feed is not None and not feed.fits(self._static)):
+      if feed is not None:
+        self._static = dict(key_shapes=key[2:4], **feed.alloc())
+      else:
+        audio, labels, pose, style = inputs
+        self._static = dict(key_shapes=key[2:4], audio=audio.clone(), labels=labels.clone(), pose=pose.clone(),
+                            style=style.clone())
       self._graphs = {}
     st = self._static
     pairs = []
-    for name, src in (('audio', audio), ('labels', labels), ('pose', pose), ('style', style)):
+    for name, src in (zip(('audio', 'labels', 'pose', 'style'), inputs) if feed is None else ()):
       # ~2 MB of device-to-device copies per step.  Always done: torch's version counters do not see writes made through
       # .data, raw-pointer kernels or DLPack producers, so "same tensor object, same version" does not prove "same batch".
       # inputs_unchanged=True is the caller's explicit promise (e.g. a profiling loop over one fixed batch).
@@ -860,7 +903,7 @@ class MixStageTrainStep:
     entry = self._graphs.get(key)
     opt = self.optim_G if k == 'G' else self.optim_D
     if entry is None:
-      entry = self._capture(key, k, st, opt)       # capture executes nothing: replay below does the step
+      entry = self._capture(key, k, st, opt, feed)       # capture executes nothing: replay below does the step
     else:
       self._consume_decisions(k)
     # this step's loss weights (the schedule moved on the host): into the device tensor the captured loss kernels read
@@ -870,6 +913,8 @@ class MixStageTrainStep:
     opt.mark_active(entry['active'])
     self._refresh_meetings()
     entry['fwd_bwd'].replay()
+    if feed is not None:
+      feed.issued()
     if entry['opt'] is not None:            # (gloo: the exchange runs eagerly between the two graphs)
       self._all_reduce(opt, entry['active'])
       entry['opt'].replay()
@@ -878,8 +923,9 @@ class MixStageTrainStep:
     ops.refresh_prepared_weights(opt.flat_p, start=entry['n_prepared'])
     self.fake_pose, self.losses = entry['fake'], entry['losses']
 
-  def _capture(self, key, k, st, opt):
+  def _capture(self, key, k, st, opt, feed=None):
     m = self.model
+    head = (lambda: feed.launch(st)) if feed is not None else None
     sched = m.lambda_scheduler
     if not (hasattr(sched, 'state') and hasattr(sched, 'set_state')):
       # the warm-up and capture passes below call scheduler.step(); their effect on the schedule has to be undone
@@ -891,6 +937,7 @@ class MixStageTrainStep:
     thresh = (m.G.thresh.value, m.G.thresh.iters)
     bn_state = {n: b.clone() for n, b in m.named_buffers()}
     drop_state = self._dropout_state.clone() if self._dropout_state is not None else None
+    draw_state = feed.save() if feed is not None else None
     # one eager pass on a side stream sizes the workspace and warms the allocator, then undo its side effects
     side = self._capture_stream
     side.wait_stream(torch.cuda.current_stream())
@@ -898,7 +945,7 @@ class MixStageTrainStep:
     layers.set_train_tape(warm_tape)
     try:
       with torch.cuda.stream(side):
-        self._forward_backward(st['audio'], st['labels'], st['pose'], st['style'], k)
+        self._forward_backward(st['audio'], st['labels'], st['pose'], st['style'], k, head)
     finally:
       layers.set_train_tape(None)
     warm_active = opt.active_params()
@@ -915,6 +962,8 @@ class MixStageTrainStep:
         b.copy_(bn_state[n])
       if drop_state is not None:
         self._dropout_state.copy_(drop_state)          # (the warm-up pass was a step of its own: its step word goes back)
+      if draw_state is not None:
+        feed.restore(draw_state)                       # (... and so does the store's cursor: the replay draws this batch again)
     for mod in warm_tape:
       mod._pending_batches -= 1
     torch.set_rng_state(rng)
@@ -932,11 +981,11 @@ class MixStageTrainStep:
       # automatic fallback here: MS_CAPTURE_ALLREDUCE=0 selects the two-graph form with the eager exchange up front)
       with torch.cuda.graph(g1, stream=side, capture_error_mode=mode):
         if one_graph and self.world > 1:
-          fake, losses = self._with_marker(self._forward_backward, st['audio'], st['labels'], st['pose'], st['style'], k)
+          fake, losses = self._with_marker(self._forward_backward, st['audio'], st['labels'], st['pose'], st['style'], k, head)
           # (the warm-up pass above ran the same forward / backward: its set of parameters with gradients is this step's)
           self._all_reduce(opt, warm_active)
         else:
-          fake, losses = self._forward_backward(st['audio'], st['labels'], st['pose'], st['style'], k)
+          fake, losses = self._forward_backward(st['audio'], st['labels'], st['pose'], st['style'], k, head)
         if one_graph:
           opt.clip_and_step(count=False)
     finally:
@@ -950,7 +999,8 @@ class MixStageTrainStep:
       with torch.cuda.graph(g2, stream=side, capture_error_mode=mode):
         opt.clip_and_step(count=False)
     entry = dict(fwd_bwd=g1, opt=g2, fake=fake, losses=losses, bn_tape=tape, active=active,
-                 n_prepared=ops.prepared_count(opt.flat_p))
+                 n_prepared=ops.prepared_count(opt.flat_p),
+                 feed=feed)       # (keeps the store and the pre-step alive: the captured draw holds their pointers, the key their ids)
     self._graphs[key] = entry
     return entry
 
